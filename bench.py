@@ -13,26 +13,37 @@ through the package's autograd functions (i.e. through the drop-in boundary, not
 Workload = BASELINE.json configs[1] per GPU: batch 16, 240x320 BRDF maps, 120x160 env grid,
 12 SG lobes, 8x16 directions.
 
-N > 1 (round 6: launch-proof).  `python bench.py --gpus N` WITHOUT torchrun re-executes itself under
+N > 1 (round 6: launch-proof).  `python bench.py --gpus N` WITHOUT torchrun runs itself as a child under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); under
 torchrun (the driver's form) it uses the RANK / LOCAL_RANK / WORLD_SIZE it finds.  Images shard across ranks (weak scaling:
 --batch images per GPU, default 16) and the timed step additionally runs the render loss (LSregressDiffSpec + masked L2,
 wrapperBRDFLight.py:170-207) with its only collective -- the all-reduce of the loss numerator / denominator pair over RCCL
  -- between forward and backward, so the N-GPU number contains the exchange north_star names.
-Like-for-like anchors, flat in `config` at EVERY N: `Mpix_layer_only` (the N = 1 headline's step, no collective) and
+Like-for-like anchors (`--full`), flat in `config` at EVERY N: `Mpix_layer_only` (the N = 1 headline's step, no collective) and
 `Mpix_with_loss` (the N > 1 headline's step); the N = 1 line also carries `scaling_anchor_Mpix_per_s` (= its with-loss figure,
 what an N-GPU `value` divides by) and leaves it in `.bench_anchor.json` for the N > 1 runs that follow on the same box.
-N > 1 legs (all ranks): `cfg4_*` = BASELINE configs[3] (8 images per GPU, batch 64 at N = 8), `strong16_*` = 16 images split
+N > 1 legs (`--full`, all ranks): `cfg4_*` = BASELINE configs[3] (8 images per GPU, batch 64 at N = 8), `strong16_*` = 16 images split
 N ways (SURVEY 8d strong scaling), `obj_ms` = the sharded light objective, `n_ranks_seen` = an RCCL all-reduce of ones.
 
-Timing: `--reps` (default 15) repetitions of the K-step loop, each bracketed by barrier + device
-synchronise on both sides and maximised over ranks; the line reports the MEDIAN repetition (`ms_per_step`).
+A PLAIN run (no `--full`) does only what the headline needs: set up, `--warmup` untimed steps and `--steps` timed steps of the
+headline step (N = 1: the layer's forward + backward; N > 1: the with-loss step), `--dump-outputs DIR` if given, the line.
+`--full` adds everything else described here: the other timed step, the per-kernel event timing and rooflines, the informational legs,
+the baselines, `bench_detail.json` and the scaling anchors.
+
+Timing: `--reps` repetitions of the K-step loop (default 1 in a plain run, so that `--steps` is the number of timed steps; 15 with
+`--full`), each bracketed by barrier + device synchronise on both sides and maximised over ranks; the line reports the MEDIAN
+repetition (`ms_per_step`).
+
+`--dump-outputs DIR`: after the timed steps, what the headline step returned in its last iteration -- the layer's env / diffuse /
+specular images and the SG gradients (N > 1: also the render loss) of rank 0 -- as DIR/<name>.npy, float32; an array larger than
+DUMP_MAX_ELEMS elements is stored as a fixed seeded sample (see dump_outputs).  The inputs are seeded, so runs with the same
+arguments see the same inputs and two builds can be compared output for output.
 
 THE LINE (round 6): <= 6 KB, `config` holds flat scalars with keys <= 40 characters and strings <= 120 (what the driver's
-record keeps); every nested object of rounds 1-5 (per-kernel rooflines, VALU records, per-mode baselines, repetitions) goes to
-`bench_detail.json` beside this file (`config.detail_file`).  tests/test_bench_contract.py asserts the limits.
+record keeps); with `--full`, every nested object of rounds 1-5 (per-kernel rooflines, VALU records, per-mode baselines, repetitions)
+goes to `bench_detail.json` beside this file (`config.detail_file`).  tests/test_bench_contract.py asserts the limits.
 
-Informational legs (single process only; they can never fail the contract line): the cascade-0 light objective fused / unfused /
+Informational legs (`--full`, single process only; they can never fail the contract line): the cascade-0 light objective fused / unfused /
 forward-only, BASELINE config 3 (the synthetic trainLight step incl. Adam; eager and HIP-graph replay), config 5, RCCL with a
 world of one (c10d route and the extension's in-stream ncclAllReduce), and the COLD column: the layer step and the objective step
 rotating through four input sets (2.4 GB, ten times the 256 MB Infinity Cache) -- what a loader handing over fresh batches sees.
@@ -47,6 +58,7 @@ import datetime
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -62,6 +74,8 @@ LINE_LIMIT = 6000        # bytes of the contract line (the driver's record keeps
 KEY_LIMIT, STR_LIMIT = 40, 120
 DETAIL_FILE = os.environ.get("SGR_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
 ANCHOR_FILE = os.path.join(ROOT, ".bench_anchor.json")
+DUMP_MAX_ELEMS = 1 << 21       # per array written by --dump-outputs (8 MB of float32); larger arrays are sampled
+DUMP_MAX_BYTES = 64 << 20      # all arrays of one --dump-outputs together
 
 
 def algorithmic_bytes_per_shaded_px(K: int, J: int, q: int) -> dict:
@@ -94,12 +108,17 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=300, help="untimed steps first (0.15 s at config 2: the GPU's clocks ramp up over the first ~100 ms of load)")
     ap.add_argument("--batch", "--per-gpu-batch", dest="batch", type=int, default=16, help="images per GPU (weak scaling; BASELINE configs[3] = 8)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: --batch is the TOTAL, split evenly over the ranks (SURVEY.md 8d config 4: 16 images 2/4/8 ways)")
-    ap.add_argument("--reps", type=int, default=15, help="repetitions of the K-step timed loop; the median is reported (fifteen: with a short --warmup the first three repetitions still run on ramping clocks)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the K-step timed loop; the median is reported (default: 1 in a plain run; "
+                                                            "15 with --full: with a short --warmup the first three repetitions still run on ramping clocks)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the other timed step, per-kernel timing and rooflines, the informational legs, "
+                                                         "the CPU / eager-GPU baselines, bench_detail.json and the scaling anchors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed step returned in its last iteration to DIR/<name>.npy "
+                                                                         "(float32; arrays above %d elements as a fixed seeded sample)" % DUMP_MAX_ELEMS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--layer-only", action="store_true", help="skip the informational legs (light objective, config 3 / 4 / 5, cold column, HIP graph, baselines): profiling and rehearsal runs")
+    ap.add_argument("--layer-only", action="store_true", help="with --full: skip the informational legs (light objective, config 3 / 4 / 5, cold column, HIP graph, baselines): profiling and rehearsal runs")
     ap.add_argument("--no-env", action="store_true", help="render-only variant (env image never materialised)")
-    ap.add_argument("--graph-leg", action="store_true", help="with --layer-only: still time the with-render-loss step replayed from a HIP graph (sgr.capture_step) -- the batch sweep's launch-bound sizes")
-    ap.add_argument("--no-config5", action="store_true", help="skip the compact BASELINE configs[4] leg of the default run")
+    ap.add_argument("--graph-leg", action="store_true", help="with --full --layer-only: still time the with-render-loss step replayed from a HIP graph (sgr.capture_step) -- the batch sweep's launch-bound sizes")
+    ap.add_argument("--no-config5", action="store_true", help="skip the compact BASELINE configs[4] leg of a --full run")
     ap.add_argument("--pmc-workload", default="layer", choices=("layer", "objective", "objective_heads"),
                     help="counter-collection runs (tools/pmc_traffic.sh, tools/pmc_sq.sh): 'objective' / 'objective_heads' run ONLY the fused light objective "
                          "+ its backward (the trainLight step's kernels: fwd_pk*gt* and sg_bwd_recon_pk_kernel; _heads: decoder outputs in, premap 3) "
@@ -123,8 +142,9 @@ def self_launch_command(gpus: int, argv) -> list:
 
 def self_launch(args) -> None:
     """Round 5 raised SystemExit here ("needs a torchrun launch"): the same command the driver uses at N = 1, with --gpus 8, died before
-    touching a GPU.  Now the process BECOMES the torchrun launcher (exec: same stdout, same exit code), after checking that the box has the
-    GPUs -- RCCL needs one per rank; SGR_BENCH_BACKEND=gloo is the flagged rehearsal on fewer."""
+    touching a GPU.  Now the process starts the torchrun launcher as a child (same stdout) and exits with its exit code, after checking that
+    the box has the GPUs -- RCCL needs one per rank; SGR_BENCH_BACKEND=gloo is the flagged rehearsal on fewer.  A child, not exec: counting
+    the devices has opened the GPU in this process, and replacing a process that holds the GPU open is not safe."""
     backend = os.environ.get("SGR_BENCH_BACKEND", "nccl")
     ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if ndev == 0:
@@ -136,7 +156,7 @@ def self_launch(args) -> None:
     print("# bench.py: --gpus %d outside torchrun -> %s" % (args.gpus, " ".join(cmd[1:8])), file=sys.stderr)
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def median(v):
@@ -160,12 +180,18 @@ class Workload:
         self.ct_s = torch.randn((bn, 3, R, C), generator=g).to(dev)
         self.layer = pkg.renderingLayer(imWidth=C, imHeight=R, envWidth=ew, envHeight=eh)
         self.ind = torch.ones(bn, 1, 1, 1, device=dev)
+        self.last = None      # keep=True: what that step returned (--dump-outputs)
 
     def sg(self, x=None):
         x = x or self.x
         return [x["axis"], x["lamb"], x["weight"]]
 
-    def step(self, ev=None, x=None, ct_env=None):
+    def _keep(self, env, d, s, grads, err=None):
+        self.last = dict(env=env, diffuse=d, spec=s, grad_axis=grads[0], grad_lamb=grads[1], grad_weight=grads[2])
+        if err is not None:
+            self.last["render_loss"] = err
+
+    def step(self, ev=None, x=None, ct_env=None, keep=False):
         """the N = 1 headline: fused forward + fused backward of the layer"""
         x = x or self.x
         ct_env = self.ct_env if ct_env is None else ct_env
@@ -178,17 +204,23 @@ class Workload:
         grads = torch.autograd.grad(outs, self.sg(x), grad_outputs=cts)
         if ev is not None:
             ev[2].record()
+        if keep:
+            self._keep(env, d, s, grads)
         return grads
 
-    def step_with_loss(self, group="default"):
+    def step_with_loss(self, group="default", keep=False):
         """the same step with the render loss in the loop (LSregressDiffSpec + masked L2 kernels, wrapperBRDFLight.py:170-207 around the
         layer); sharded: the all-reduce of [num, den] sits between forward and backward -- the N > 1 headline"""
         x, group = self.x, (self.group if group == "default" else group)
         env, d, s = self.layer.forwardSG(x["albedo"], x["normal"], x["rough"], x["axis"], x["lamb"], x["weight"], need_env=self.need_env)
         err, _ = self.pkg.render_loss(d, s, x["im"], x["seg"], self.R, self.C, group=group)
         if self.need_env:
-            return torch.autograd.grad([err, env], self.sg(), grad_outputs=[None, self.ct_env])
-        return torch.autograd.grad([err], self.sg())
+            grads = torch.autograd.grad([err, env], self.sg(), grad_outputs=[None, self.ct_env])
+        else:
+            grads = torch.autograd.grad([err], self.sg())
+        if keep:
+            self._keep(env, d, s, grads, err)
+        return grads
 
     def step_objective(self, group="default", x=None):
         """the cascade-0 light objective (render loss + 10 x env reconstruction loss, wrapperBRDFLight.py:167-207), fused, fwd + bwd"""
@@ -198,7 +230,7 @@ class Workload:
         return torch.autograd.grad(obj, self.sg(x))
 
     def release(self):
-        self.x = self.ct_env = self.ct_d = self.ct_s = None
+        self.x = self.ct_env = self.ct_d = self.ct_s = self.last = None
 
 
 def clip(v, n=STR_LIMIT):
@@ -207,6 +239,8 @@ def clip(v, n=STR_LIMIT):
 
 def main() -> None:
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                      # does not return
     emit = _claim_stdout()
@@ -262,7 +296,6 @@ def main() -> None:
     # different images on every rank (seed offset), generated on the CPU like SURVEY 8d prescribes
     wl = Workload(pkg, O, dev, bn, dims, 20202 + 1000 * rank, need_env, group)
     x, layer = wl.x, wl.layer
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
 
     if args.pmc_workload != "layer":      # counter-collection workload: the objective's kernels alone
         heads = args.pmc_workload == "objective_heads"
@@ -284,12 +317,15 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn, steps, events=None):
-        """EXACTLY `steps` steps between two barrier + synchronise brackets; seconds, max over ranks."""
+    def timed(fn, steps, events=None, keep=False):
+        """EXACTLY `steps` steps between two barrier + synchronise brackets; seconds, max over ranks.  keep: the last step keeps its outputs."""
         barrier()
         t0 = time.perf_counter()
-        for i in range(steps):
+        n = steps - 1 if keep else steps
+        for i in range(n):
             fn(events[i]) if events is not None else fn()
+        if keep:
+            fn(events[n], keep=True) if events is not None else fn(keep=True)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -298,24 +334,37 @@ def main() -> None:
             dt = t.item()
         return dt
 
-    for _ in range(args.warmup):
-        wl.step()
-        wl.step_with_loss()
-
-    reps = max(1, args.reps)
-    fwd_acc = bwd_acc = 0.0
-    plain_dts, loss_dts = [], []
-    for _ in range(reps):
-        plain_dts.append(timed(wl.step, args.steps, ev))
-        fwd_acc += sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
-        bwd_acc += sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
-    for _ in range(reps):
-        loss_dts.append(timed(wl.step_with_loss, args.steps))
-    fwd_ms, bwd_ms = fwd_acc / reps, bwd_acc / reps
-    plain_ms, loss_step_ms = median(plain_dts) / args.steps * 1e3, median(loss_dts) / args.steps * 1e3
     # the contract line: single GPU = the layer's forward + backward; sharded = the same plus the loss and its all-reduce
+    full = args.full
+    reps = max(1, args.reps if args.reps is not None else (15 if full else 1))
+    dump = args.dump_outputs is not None
+    plain_dts, loss_dts = [], []
+    if full:
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+        for _ in range(args.warmup):
+            wl.step()
+            wl.step_with_loss()
+        fwd_acc = bwd_acc = 0.0
+        for r in range(reps):
+            plain_dts.append(timed(wl.step, args.steps, ev, keep=dump and world == 1 and r == reps - 1))
+            fwd_acc += sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
+            bwd_acc += sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
+        for r in range(reps):
+            loss_dts.append(timed(wl.step_with_loss, args.steps, keep=dump and world > 1 and r == reps - 1))
+        fwd_ms, bwd_ms = fwd_acc / reps, bwd_acc / reps
+        plain_ms, loss_step_ms = median(plain_dts) / args.steps * 1e3, median(loss_dts) / args.steps * 1e3
+    else:      # a plain run: the headline step alone, --warmup untimed and --steps timed (per repetition)
+        headline_step = wl.step if world == 1 else wl.step_with_loss
+        for _ in range(args.warmup):
+            headline_step()
+        for r in range(reps):
+            (plain_dts if world == 1 else loss_dts).append(timed(headline_step, args.steps, keep=dump and r == reps - 1))
     headline_dts = plain_dts if world == 1 else loss_dts
     dt = median(headline_dts)
+    if dump:
+        if rank == 0:
+            dump_outputs(wl.last, args.dump_outputs)
+        wl.last = None
 
     # The informational legs keep their own loop lengths: at least 60 timed iterations after 10 untimed ones, whatever --steps / --warmup say.
     # With the driver's `--steps 20 --warmup 5` a 20-iteration loop of a 0.5 ms step is 10 ms -- shorter than the ~100 ms the clocks take
@@ -328,7 +377,7 @@ def main() -> None:
         return timed(fn, n) / n * 1e3
 
     flat, detail = {}, {}      # flat: scalars for `config` (keys <= 40 chars); detail: everything nested -> bench_detail.json
-    legs = need_env and not args.layer_only and args.config == 2
+    legs = full and need_env and not args.layer_only and args.config == 2
 
     # ---- N > 1 legs: every rank takes part, in the same order (a leg that one rank skipped would leave the others in its barrier) ----------
     if world > 1 and legs:
@@ -420,7 +469,7 @@ def main() -> None:
 
     # informational: the with-render-loss step replayed from a HIP graph (sgr.capture_step): what a launch-bound caller -- the reference's
     # default batch of 5, trainLight.py:28 -- gets by capturing its step
-    if world == 1 and (args.graph_leg or legs):
+    if world == 1 and full and (args.graph_leg or legs):
         try:
             captured = pkg.capture_step(wl.step_with_loss)
             captured.replay()
@@ -465,27 +514,6 @@ def main() -> None:
         img_px = bn * imH * imW
         ms_per_step = dt / args.steps * 1e3
         value = world * img_px / (dt / args.steps) / 1e6
-        bpp = algorithmic_bytes_per_shaded_px(K, J, q)
-        fwd_bytes = P * (bpp["fwd_env"] if need_env else bpp["fwd_noenv"])
-        bwd_bytes = P * (bpp["bwd_sg"] if need_env else bpp["bwd_sg"] - 3 * J * 4)
-        fwd_gbps = fwd_bytes / (fwd_ms * 1e-3) / 1e9
-        bwd_gbps = bwd_bytes / (bwd_ms * 1e-3) / 1e9
-        dom = ("bwd", bwd_ms, bwd_bytes, bwd_gbps) if bwd_ms >= fwd_ms else ("fwd", fwd_ms, fwd_bytes, fwd_gbps)
-        # HBM bytes per launch of the dominant kernel from the PMC passes (tools/pmc_traffic.sh -> tools/parse_pmc.py ->
-        # profiles/traffic.json), recorded per WORKLOAD (config, batch, env written or not): a figure measured on another
-        # workload is not reported
-        tkey = f"config{args.config}_batch{bn}_{'env' if need_env else 'noenv'}"
-        want = [r"sg_bwd_pk_kernel<"] if dom[0] == "bwd" else [r"fwd_pk_half_kernel<", r"fwd_pk_kernel<"]
-        traffic, dom_name, traffic_stale = pmc_traffic(tkey, want)
-        if dom_name is None:
-            dom_name = ("sg_bwd" if dom[0] == "bwd" else "fwd") + " kernel (no PMC record for this workload)"
-        # the resource that actually binds the fused kernels: VALU issue.  SQ counters of the same workload (tools/pmc_sq.sh ->
-        # profiles/sq.json): SQ_ACTIVE_INST_VALU counts, per SIMD quad, the cycles a VALU instruction is in flight; x 4 / SIMDs
-        # against the kernel's duration in shader-clock cycles (per-shader-engine SQ_BUSY_CYCLES, tools/parse_sq.py) is the fraction of
-        # issue cycles used.  Both records are OFFLINE (counter passes cannot run inside the timed loop) and stamped with the hash of
-        # the kernel sources they were measured on: a record from other sources is reported as stale and does not decide `limited_by`
-        valu = valu_roofline(tkey, want, dom[1])
-        limited_by = limited(valu, dom[3] / HBM_PEAK_GBPS)
         mpix = lambda ms: round(world * img_px / (ms * 1e-3) / 1e6, 1)
         cfg_idx = 1 if args.config == 2 else 4
         config = {
@@ -497,28 +525,8 @@ def main() -> None:
             "shaded_px_per_step_per_gpu": P, "image_px_per_step_per_gpu": img_px, "q": q,
             "Mshade_per_s": round(world * P / (dt / args.steps) / 1e6, 1),
             "repetitions": reps, "statistic": "median repetition of the K-step loop, max over ranks",
-            "ms_layer_only": round(plain_ms, 4), "Mpix_layer_only": mpix(plain_ms),
-            "ms_with_loss": round(loss_step_ms, 4), "Mpix_with_loss": mpix(loss_step_ms),
-            "fwd_us": round(fwd_ms * 1e3, 1), "bwd_us": round(bwd_ms * 1e3, 1),
-            "fwd_frac": round(fwd_gbps / HBM_PEAK_GBPS, 4), "bwd_frac": round(bwd_gbps / HBM_PEAK_GBPS, 4),
-            "legs_timed_iterations": leg_steps, "legs_untimed_iterations": leg_warmup,
+            "full": full,
         }
-        # the like-for-like anchor of an N-GPU `value` (whose step carries the render loss): the N = 1 with-loss figure
-        anchor_key = f"cfg{args.config}_b{bn}_{'env' if need_env else 'noenv'}"
-        if world == 1:
-            config["scaling_anchor_Mpix_per_s"] = mpix(loss_step_ms)
-            if not args.strong:
-                _write_anchor(anchor_key, dict(Mpix_with_loss=mpix(loss_step_ms), Mpix_layer_only=mpix(plain_ms), cfg4_Mpix_per_s=flat.get("cfg4_Mpix_per_s"),
-                                               obj_ms=flat.get("obj_ms")))
-        else:
-            a = _read_anchor(f"cfg{args.config}_b{16 if args.strong else bn}_{'env' if need_env else 'noenv'}")
-            config["scaling_anchor_Mpix_per_s"] = a.get("Mpix_with_loss")
-            config["anchor_Mpix_layer_only"] = a.get("Mpix_layer_only")
-            config["anchor_cfg4_Mpix_per_s"] = a.get("cfg4_Mpix_per_s")
-            config["anchor_source"] = a.get("source")
-        config.update({k: v for k, v in flat.items()})
-        config["rehearsal"] = None if backend == "nccl" else clip(f"backend {backend}, {ndev} GPU(s) for {world} ranks: the N > 1 flow only, not a measurement")
-        config["detail_file"] = os.path.basename(DETAIL_FILE)
         out = {
             "metric": "Mpix/s shaded (fwd+bwd), 240x320x12-SG render layer" if args.config == 2 else "Mpix/s shaded (fwd+bwd), 480x640x24-SG 16x32 render layer (stress config)",
             "value": round(value, 1),
@@ -533,54 +541,124 @@ def main() -> None:
             "dtype": "f32",
             "data": "synthetic",
             "config": config,
-            "roofline": {"bound": "hbm", "kernel": clip(dom_name, 80), "achieved": round(dom[3], 1), "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": round(dom[3] / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_record_stale": traffic_stale,
-                         "algorithmic_bytes_per_launch": dom[2], "avg_launch_ms": round(dom[1], 4),
-                         "limited_by": limited_by},
         }
-        if valu is not None:      # compact; the full record (per-wave cycle shares, instruction counts, the source note) -> bench_detail.json
-            out["roofline_valu"] = {k: valu.get(k) for k in ("bound", "kernel", "frac", "frac_at_max_clock", "effective_clock_GHz", "pmc_kernel_ms",
-                                                             "live_kernel_ms", "record", "record_stale")}
-            out["roofline_valu"]["kernel"] = clip(out["roofline_valu"]["kernel"], 80)
-        detail["roofline_valu"] = valu
-        detail["ms_per_step_repetitions"] = [round(t / args.steps * 1e3, 4) for t in headline_dts]
-        detail["ms_layer_only_repetitions"] = [round(t / args.steps * 1e3, 4) for t in plain_dts]
-        detail["ms_with_loss_repetitions"] = [round(t / args.steps * 1e3, 4) for t in loss_dts]
-        detail["kernels"] = {"forward (sgr_fused_fwd)": {"ms": round(fwd_ms, 4), "GBps": round(fwd_gbps, 1), "frac": round(fwd_gbps / HBM_PEAK_GBPS, 4), "bytes": fwd_bytes},
-                             "backward (sgr_fused_bwd_sg)": {"ms": round(bwd_ms, 4), "GBps": round(bwd_gbps, 1), "frac": round(bwd_gbps / HBM_PEAK_GBPS, 4), "bytes": bwd_bytes}}
-        if world == 1 and not args.no_cpu_baseline and not args.layer_only and args.config == 2:
-            cb = cpu_baseline(O, 240, 320, 120, 160, 12, 8, 16)
-            # port vs the UNMODIFIED reference on the same cores, measured where the reference exists (the authoring
-            # container; oracle/calibrate_port_vs_reference.py -> profiles/cpu_calibration.json)
+        if full:
+            full_line(out, args, O, dev, world, bn, need_env, K, J, q, P, mpix, fwd_ms, bwd_ms, plain_ms, loss_step_ms, leg_steps, leg_warmup,
+                      flat, detail, headline_dts, plain_dts, loss_dts)
+        config["rehearsal"] = None if backend == "nccl" else clip(f"backend {backend}, {ndev} GPU(s) for {world} ranks: the N > 1 flow only, not a measurement")
+        if full:
+            config["detail_file"] = os.path.basename(DETAIL_FILE)
+            detail["line"] = out
             try:
-                cal = json.load(open(os.path.join(ROOT, "profiles", "cpu_calibration.json")))
-            except Exception:
-                cal = None
-            detail["cpu_baseline"] = dict(cb, calibration=cal)
-            ratio = ((cal or {}).get("modes", {}).get("fwd_bwd_sg", {}) or {}).get("broadcast_port_over_reference_speed")
-            out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
-                                   "sample": clip(cb["sample_short"]), "cpu": clip(cb["cpu"], 60),
-                                   "fwd_only_Mpix_per_s": cb["modes"]["forward_only"]["Mpix_per_s"],
-                                   "all_grads_Mpix_per_s": cb["modes"]["fwd_bwd_all_grads"]["Mpix_per_s"]}
-            if cb["kind"] == "port" and ratio:      # an ESTIMATE: the ratio was measured on the authoring container's CPU, not this one
-                out["cpu_baseline"]["port_over_reference_speed"] = ratio
-                out["cpu_baseline"]["reference_estimate_Mpix_per_s"] = round(cb["value"] / ratio, 4)
-            try:
-                eg = eager_gpu_baseline(O, dev, 240, 320, 120, 160, 12, 8, 16)
-                detail["eager_gpu_baseline"] = eg
-                out["eager_gpu_baseline"] = {"value": eg["value"], "unit": eg["unit"], "kind": eg["kind"]}
-            except Exception as exc:       # informational leg: never fail the bench over it
-                out["eager_gpu_baseline"] = {"error": str(exc)[:120]}
-        detail["line"] = out
-        try:
-            with open(DETAIL_FILE, "w") as fh:
-                json.dump(detail, fh, indent=1)
-        except OSError as exc:
-            print(f"# bench_detail.json not written: {exc}", file=sys.stderr)
+                with open(DETAIL_FILE, "w") as fh:
+                    json.dump(detail, fh, indent=1)
+            except OSError as exc:
+                print(f"# bench_detail.json not written: {exc}", file=sys.stderr)
         emit(fit_line(out))
 
     if world > 1:
         dist.destroy_process_group()
+
+
+def full_line(out, args, O, dev, world, bn, need_env, K, J, q, P, mpix, fwd_ms, bwd_ms, plain_ms, loss_step_ms, leg_steps, leg_warmup,
+              flat, detail, headline_dts, plain_dts, loss_dts) -> None:
+    """`--full`: the rest of the line -- both timed steps, the per-kernel event timing against the HBM roofline, the offline counter
+    records, the informational legs (`flat`), the scaling anchors, the baselines -- and the nested records for bench_detail.json (`detail`)."""
+    config = out["config"]
+    bpp = algorithmic_bytes_per_shaded_px(K, J, q)
+    fwd_bytes = P * (bpp["fwd_env"] if need_env else bpp["fwd_noenv"])
+    bwd_bytes = P * (bpp["bwd_sg"] if need_env else bpp["bwd_sg"] - 3 * J * 4)
+    fwd_gbps = fwd_bytes / (fwd_ms * 1e-3) / 1e9
+    bwd_gbps = bwd_bytes / (bwd_ms * 1e-3) / 1e9
+    dom = ("bwd", bwd_ms, bwd_bytes, bwd_gbps) if bwd_ms >= fwd_ms else ("fwd", fwd_ms, fwd_bytes, fwd_gbps)
+    # HBM bytes per launch of the dominant kernel from the PMC passes (tools/pmc_traffic.sh -> tools/parse_pmc.py ->
+    # profiles/traffic.json), recorded per WORKLOAD (config, batch, env written or not): a figure measured on another
+    # workload is not reported
+    tkey = f"config{args.config}_batch{bn}_{'env' if need_env else 'noenv'}"
+    want = [r"sg_bwd_pk_kernel<"] if dom[0] == "bwd" else [r"fwd_pk_half_kernel<", r"fwd_pk_kernel<"]
+    traffic, dom_name, traffic_stale = pmc_traffic(tkey, want)
+    if dom_name is None:
+        dom_name = ("sg_bwd" if dom[0] == "bwd" else "fwd") + " kernel (no PMC record for this workload)"
+    # the resource that actually binds the fused kernels: VALU issue.  SQ counters of the same workload (tools/pmc_sq.sh ->
+    # profiles/sq.json): SQ_ACTIVE_INST_VALU counts, per SIMD quad, the cycles a VALU instruction is in flight; x 4 / SIMDs
+    # against the kernel's duration in shader-clock cycles (per-shader-engine SQ_BUSY_CYCLES, tools/parse_sq.py) is the fraction of
+    # issue cycles used.  Both records are OFFLINE (counter passes cannot run inside the timed loop) and stamped with the hash of
+    # the kernel sources they were measured on: a record from other sources is reported as stale and does not decide `limited_by`
+    valu = valu_roofline(tkey, want, dom[1])
+    limited_by = limited(valu, dom[3] / HBM_PEAK_GBPS)
+    config["ms_layer_only"], config["Mpix_layer_only"] = round(plain_ms, 4), mpix(plain_ms)
+    config["ms_with_loss"], config["Mpix_with_loss"] = round(loss_step_ms, 4), mpix(loss_step_ms)
+    config["fwd_us"], config["bwd_us"] = round(fwd_ms * 1e3, 1), round(bwd_ms * 1e3, 1)
+    config["fwd_frac"], config["bwd_frac"] = round(fwd_gbps / HBM_PEAK_GBPS, 4), round(bwd_gbps / HBM_PEAK_GBPS, 4)
+    config["legs_timed_iterations"], config["legs_untimed_iterations"] = leg_steps, leg_warmup
+    # the like-for-like anchor of an N-GPU `value` (whose step carries the render loss): the N = 1 with-loss figure
+    anchor_key = f"cfg{args.config}_b{bn}_{'env' if need_env else 'noenv'}"
+    if world == 1:
+        config["scaling_anchor_Mpix_per_s"] = mpix(loss_step_ms)
+        if not args.strong:
+            _write_anchor(anchor_key, dict(Mpix_with_loss=mpix(loss_step_ms), Mpix_layer_only=mpix(plain_ms), cfg4_Mpix_per_s=flat.get("cfg4_Mpix_per_s"),
+                                           obj_ms=flat.get("obj_ms")))
+    else:
+        a = _read_anchor(f"cfg{args.config}_b{16 if args.strong else bn}_{'env' if need_env else 'noenv'}")
+        config["scaling_anchor_Mpix_per_s"] = a.get("Mpix_with_loss")
+        config["anchor_Mpix_layer_only"] = a.get("Mpix_layer_only")
+        config["anchor_cfg4_Mpix_per_s"] = a.get("cfg4_Mpix_per_s")
+        config["anchor_source"] = a.get("source")
+    config.update({k: v for k, v in flat.items()})
+    out["roofline"] = {"bound": "hbm", "kernel": clip(dom_name, 80), "achieved": round(dom[3], 1), "peak": HBM_PEAK_GBPS,
+                       "unit": "GB/s", "frac": round(dom[3] / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_record_stale": traffic_stale,
+                       "algorithmic_bytes_per_launch": dom[2], "avg_launch_ms": round(dom[1], 4),
+                       "limited_by": limited_by}
+    if valu is not None:      # compact; the full record (per-wave cycle shares, instruction counts, the source note) -> bench_detail.json
+        out["roofline_valu"] = {k: valu.get(k) for k in ("bound", "kernel", "frac", "frac_at_max_clock", "effective_clock_GHz", "pmc_kernel_ms",
+                                                         "live_kernel_ms", "record", "record_stale")}
+        out["roofline_valu"]["kernel"] = clip(out["roofline_valu"]["kernel"], 80)
+    detail["roofline_valu"] = valu
+    detail["ms_per_step_repetitions"] = [round(t / args.steps * 1e3, 4) for t in headline_dts]
+    detail["ms_layer_only_repetitions"] = [round(t / args.steps * 1e3, 4) for t in plain_dts]
+    detail["ms_with_loss_repetitions"] = [round(t / args.steps * 1e3, 4) for t in loss_dts]
+    detail["kernels"] = {"forward (sgr_fused_fwd)": {"ms": round(fwd_ms, 4), "GBps": round(fwd_gbps, 1), "frac": round(fwd_gbps / HBM_PEAK_GBPS, 4), "bytes": fwd_bytes},
+                         "backward (sgr_fused_bwd_sg)": {"ms": round(bwd_ms, 4), "GBps": round(bwd_gbps, 1), "frac": round(bwd_gbps / HBM_PEAK_GBPS, 4), "bytes": bwd_bytes}}
+    if world == 1 and not args.no_cpu_baseline and not args.layer_only and args.config == 2:
+        cb = cpu_baseline(O, 240, 320, 120, 160, 12, 8, 16)
+        # port vs the UNMODIFIED reference on the same cores, measured where the reference exists (the authoring
+        # container; oracle/calibrate_port_vs_reference.py -> profiles/cpu_calibration.json)
+        try:
+            cal = json.load(open(os.path.join(ROOT, "profiles", "cpu_calibration.json")))
+        except Exception:
+            cal = None
+        detail["cpu_baseline"] = dict(cb, calibration=cal)
+        ratio = ((cal or {}).get("modes", {}).get("fwd_bwd_sg", {}) or {}).get("broadcast_port_over_reference_speed")
+        out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
+                               "sample": clip(cb["sample_short"]), "cpu": clip(cb["cpu"], 60),
+                               "fwd_only_Mpix_per_s": cb["modes"]["forward_only"]["Mpix_per_s"],
+                               "all_grads_Mpix_per_s": cb["modes"]["fwd_bwd_all_grads"]["Mpix_per_s"]}
+        if cb["kind"] == "port" and ratio:      # an ESTIMATE: the ratio was measured on the authoring container's CPU, not this one
+            out["cpu_baseline"]["port_over_reference_speed"] = ratio
+            out["cpu_baseline"]["reference_estimate_Mpix_per_s"] = round(cb["value"] / ratio, 4)
+        try:
+            eg = eager_gpu_baseline(O, dev, 240, 320, 120, 160, 12, 8, 16)
+            detail["eager_gpu_baseline"] = eg
+            out["eager_gpu_baseline"] = {"value": eg["value"], "unit": eg["unit"], "kind": eg["kind"]}
+        except Exception as exc:       # informational leg: never fail the bench over it
+            out["eager_gpu_baseline"] = {"error": str(exc)[:120]}
+
+
+def dump_outputs(outs: dict, out_dir: str) -> None:
+    """`--dump-outputs DIR`: each array of `outs` (what the timed step returned in its last iteration) as DIR/<name>.npy, float32.  An
+    array of more than DUMP_MAX_ELEMS elements (fewer when many arrays share DUMP_MAX_BYTES) is stored as a fixed sample: its flattened
+    elements at the indices np.sort(np.random.default_rng(0).choice(numel, cap, replace=False)) -- the same indices in every run for
+    the same shape, so that two builds compare element for element."""
+    import numpy as np
+    outs = {k: v for k, v in outs.items() if v is not None}
+    cap = min(DUMP_MAX_ELEMS, DUMP_MAX_BYTES // 4 // max(1, len(outs)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outs.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def fit_line(out: dict) -> str:

@@ -189,3 +189,41 @@ def test_anchor_file_round_trip(tmp_path, monkeypatch):
     monkeypatch.setenv("SGR_BENCH_NO_ANCHOR", "1")
     b._write_anchor("cfg2_b8_env", dict(Mpix_with_loss=1.0))
     assert "cfg2_b8_env" not in json.load(open(b.ANCHOR_FILE))
+
+
+# --------------------------------------------------------------------------- #
+# the plain run and --dump-outputs                                              #
+# --------------------------------------------------------------------------- #
+def test_plain_run_flags():
+    """A plain run times exactly --steps steps once (one repetition); --full restores the fifteen repetitions and the legs."""
+    b = _bench()
+    a = b.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not a.full and a.reps is None and a.dump_outputs is None and a.steps == 7
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_within_the_cap_and_samples_the_same_elements(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn((b.DUMP_MAX_ELEMS + 12345,), generator=g)
+    outs = dict(env=big.reshape(-1, 5) if big.numel() % 5 == 0 else big, diffuse=torch.randn((2, 3, 4, 5), generator=g), spec=None,
+                render_loss=torch.tensor(0.25, dtype=torch.float64))
+    b.dump_outputs(outs, str(tmp_path / "a"))
+    b.dump_outputs(dict(outs, env=outs["env"] * 2.0), str(tmp_path / "b"))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["diffuse.npy", "env.npy", "render_loss.npy"]
+    total = 0
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype == np.float32
+        total += x.nbytes
+    assert total <= b.DUMP_MAX_BYTES
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "diffuse.npy"), outs["diffuse"].numpy())
+    assert float(np.load(tmp_path / "a" / "render_loss.npy")) == 0.25
+    e1, e2 = np.load(tmp_path / "a" / "env.npy"), np.load(tmp_path / "b" / "env.npy")
+    assert e1.shape == (b.DUMP_MAX_ELEMS,)
+    np.testing.assert_array_equal(e2, 2.0 * e1)          # the same elements sampled in both runs
+    assert np.isin(e1[:100], big.numpy()).all()

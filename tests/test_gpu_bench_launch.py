@@ -32,7 +32,7 @@ def _run(args, extra_env=None, timeout=850):
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("n", [2, 4])
 def test_bench_launches_itself_for_n_gpus_rehearsal(n, tmp_path):
-    p = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--reps", "1", "--layer-only", "--batch", "2"],
+    p = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--reps", "1", "--full", "--layer-only", "--batch", "2"],
              {"SGR_BENCH_BACKEND": "gloo", "SGR_BENCH_DETAIL": str(tmp_path / "detail.json")})
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -88,7 +88,7 @@ def test_bench_n2_over_rccl_refuses_a_one_gpu_box_loudly():
 @pytest.mark.timeout(900)
 def test_full_line_fits_the_drivers_record(tmp_path):
     detail = tmp_path / "detail.json"
-    p = _run(["--steps", "3", "--warmup", "3", "--reps", "2", "--no-cpu-baseline", "--no-config5"], {"SGR_BENCH_DETAIL": str(detail)})
+    p = _run(["--steps", "3", "--warmup", "3", "--reps", "2", "--full", "--no-cpu-baseline", "--no-config5"], {"SGR_BENCH_DETAIL": str(detail)})
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -110,3 +110,32 @@ def test_full_line_fits_the_drivers_record(tmp_path):
     for k in ("config3", "rccl_world1", "kernels", "ms_per_step_repetitions"):
         assert k in d, k
     assert "native_error" not in d["rccl_world1"], d["rccl_world1"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run: the headline step only (--steps timed steps, one repetition), a lean line, and --dump-outputs: the last timed step's
+    env / diffuse / specular images and SG gradients as float32 .npy files, 64 MB at most, the same inputs in every run."""
+    import numpy as np
+    detail = tmp_path / "detail.json"
+    p = _run(["--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")], {"SGR_BENCH_DETAIL": str(detail)})
+    assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = check_line_limits(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["config"]["repetitions"] == 1 and out["config"]["full"] is False
+    assert out["unit"] == "Mpix/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["ms_per_step"] > 0
+    assert abs(out["value"] - 16 * 240 * 320 / (out["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * out["value"]
+    assert "roofline" not in out and "cpu_baseline" not in out and "ms_with_loss" not in out["config"] and "obj_ms" not in out["config"]
+    assert not detail.exists()
+    files = sorted(f.name for f in (tmp_path / "out").iterdir())
+    assert files == ["diffuse.npy", "env.npy", "grad_axis.npy", "grad_lamb.npy", "grad_weight.npy", "spec.npy"], files
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / "out" / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "out" / "diffuse.npy").shape == (16, 3, 120, 160)

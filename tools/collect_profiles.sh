@@ -1,7 +1,7 @@
 #!/bin/bash
-# copy one tools/gpu_final.sh session from gpurun_out/ (scratch) into profiles/ under a tag:  tools/collect_profiles.sh r04l
+# copy one tools/gpu_final.sh session from its output folder (SGR_OUT_DIR, default bench_out/) into profiles/ under a tag:  tools/collect_profiles.sh r04l
 set -eu
-T=$1; G=gpurun_out; P=profiles
+T=$1; G=${SGR_OUT_DIR:-bench_out}; P=profiles
 last() { tail -1 "$1" > "$2"; }
 last $G/bench.txt $P/${T}_bench.json
 last $G/bench_warmup5.txt $P/${T}_bench_warmup5.json
