@@ -1,9 +1,8 @@
 """One image of BASELINE config 2 (240x320 BRDF maps -> 120x160 env grid, SGNum 12, 8x16 directions) through the
 UNMODIFIED reference, fp32 and fp64, forward and backward.  TEST INFRASTRUCTURE ONLY (authoring container):
 
-    python -m oracle.make_golden_fullsize       # writes tests/golden/g7_cfg2_one_image.npz
-
-    python -m oracle.make_golden_fullsize       # writes tests/golden/g7_cfg2_one_image.npz and g9_ratio1_unit_normals.npz
+    python -m oracle.make_golden_fullsize           # writes tests/golden/g7_cfg2_one_image.npz, g9_ratio1_unit_normals.npz and g12_cfg2_objective.npz
+    python -m oracle.make_golden_fullsize g12       # writes g12 alone (the others are left untouched); any subset of g7 g9 g12
 
 The inputs and cotangents are the seeded synthetic ones of SURVEY.md section 8d drawn from NumPy's frozen legacy stream
 (``oracle.sg_oracle.synthetic_inputs_np`` -- round 5: torch's CPU generator is an implementation detail of the installed torch, and
@@ -14,6 +13,7 @@ full-size GPU tests bound the error against the fp64 oracle by the REFERENCE's o
 from __future__ import annotations
 
 import os
+import sys
 
 import numpy as np
 import torch
@@ -77,11 +77,65 @@ def kink_fixture():
         print(f"  reference fp32 vs fp64 glin_{k:7s} rel-L2 all pixels {((a - b).norm() / b.norm()).item():.2e}   where the branches agree {((a[m] - b[m]).norm() / b[m].norm()).item():.2e}")
 
 
+# g12 (round 7): the training OBJECTIVE of config 2 at size -- renderErr + 10 reconstErr (wrapperBRDFLight.py:167-207, trainLight.py:237) of the
+# image of g7 (same CFG, same seed: the tests regenerate the inputs with synthetic_inputs_np), with env_ind = 1, evaluated by the reference in
+# fp32 and fp64 (oracle.make_golden.run_reference).  Stored: the loss values and the render loss's numerator / denominator (float64 scalars),
+# the rendered image whole, and the gradients of the total w.r.t. the SG parameters sub-sampled at S12 with their full-tensor norms.  The
+# stride is 5, not g7's 3: a committed file stays within 1 MiB, and 768 of the 19 200 env cells (all K lobes of each) still sample every
+# region of the grid.
+S12 = 5
+LOSS_KEYS = ("im", "seg", "env_gt")
+
+
+def checksums_loss(inp):
+    return np.array([inp[k].double().sum().item() for k in LOSS_KEYS])
+
+
+def objective_blob(r32, r64, inp):
+    keys = sorted(k for k in CFG if k not in ("flavour", "rng"))
+    blob = dict(cfg_keys=np.array(keys), cfg_vals=np.array([float(CFG[k]) for k in keys]), stride_sg=np.array([S12]),
+                in_checksums=checksums(inp), in_checksums_loss=checksums_loss(inp))
+    for tag, r in (("ref32", r32), ("ref64", r64)):
+        for k in ("render_err", "recon_err", "render_num", "render_den"):
+            blob[f"{tag}_{k}"] = r[k].detach().double().numpy()
+        blob[f"{tag}_rendered"] = r["rendered"].detach().numpy().astype(np.float32)
+        for k in ("axis", "lamb", "weight"):
+            g = r[f"gtot_{k}"].detach()
+            blob[f"{tag}_gtot_{k}"] = g[..., ::S12, ::S12].numpy().astype(np.float32)
+            blob[f"{tag}_gtot_{k}_norm"] = np.array([g.double().norm().item()])
+    return blob
+
+
+def objective_fixture():
+    inp = MG.make_inputs(CFG)
+    r32, _ = MG.run_reference(CFG, inp, torch.float32)
+    r64, _ = MG.run_reference(CFG, inp, torch.float64)
+    blob = objective_blob(r32, r64, inp)
+    path = os.path.join(OUT, "g12_cfg2_objective.npz")
+    np.savez_compressed(path, **blob)
+    print("wrote", path, f"{os.path.getsize(path) / 1e6:.2f} MB")
+    for k in ("render_err", "recon_err", "render_num", "render_den"):
+        print(f"  reference fp32 vs fp64 {k:12s} {blob['ref32_' + k][0]:.9g} {blob['ref64_' + k][0]:.9g}")
+    for k in ("rendered", "gtot_axis", "gtot_lamb", "gtot_weight"):
+        a, b = torch.from_numpy(blob["ref32_" + k]).double(), torch.from_numpy(blob["ref64_" + k]).double()
+        print(f"  reference fp32 vs fp64 {k:12s} rel-L2 {((a - b).norm() / b.norm()).item():.2e}")
+    return blob
+
+
 def main():
     if not RI.available():
         raise SystemExit("reference not mounted")
     torch.set_num_threads(8)
-    kink_fixture()
+    only = set(sys.argv[1:])     # e.g. `python -m oracle.make_golden_fullsize g12`: leave g7 / g9 untouched
+    unknown = only - {"g7", "g9", "g12"}
+    if unknown:
+        raise SystemExit(f"unknown fixture(s) {sorted(unknown)}; choose from g7 g9 g12")
+    if not only or "g9" in only:
+        kink_fixture()
+    if not only or "g12" in only:
+        objective_fixture()
+    if only and "g7" not in only:
+        return
     inp = MG.make_inputs(CFG)
     r32, cts = MG.run_reference(CFG, inp, torch.float32)
     r64, _ = MG.run_reference(CFG, inp, torch.float64)

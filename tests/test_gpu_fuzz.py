@@ -23,7 +23,12 @@ N_CASES = 30
 # e_ref of this file -- is ONE sample of that noise and came out at 4e-5 where the kernels' sample was 1.3e-4 (case 16 with F0 = 0.115; the
 # fused and the unfused HIP routes agree to 1e-7 there, each pixel but one within 1e-7).  So for q = 1 the objective's gradient bound has
 # the reference-made yardstick as its floor: max(2 e_proxy, 2 x 1.78e-4); the layer-level quantities keep max(2 e_proxy, 1e-4).
+# Round 7: the floor covers only the gradients that need it.  Measured over the thirty cases (error vs fp64, fp32 oracle's own), worst per
+# gradient -- q = 1: g_axis 1.33e-4 (3.99e-5, case 16), g_lamb 1.24e-4 (3.68e-5, case 16), g_weight 5.09e-5 (5.05e-5, case 12);
+# q = 2: g_axis 2.84e-5, g_lamb 3.97e-5, g_weight 6.03e-5 (case 17, each within its fp32 oracle's own).  g_weight meets max(2 e_proxy, 1e-4)
+# in every case with a factor 2 to spare and keeps it; g_lamb (the a . S - w . q path) exceeds it at case 16 as g_axis does, so both keep the floor.
 E_REF_SPEC_RATIO1 = 1.78e-4
+RATIO1_FLOOR = ("axis", "lamb")
 
 
 def _cases():
@@ -100,13 +105,16 @@ def test_random_case_vs_oracle(sgr, c):
     r3, c3, g3 = _objective_oracle(O, inp, ind, R, C, eh, ew, torch.float32, fov, F0, cam)
     assert scalar_close(obj[1].item(), ro.item(), r3.item() - ro.item()), (c, "renderErr", obj[1].item(), ro.item(), r3.item())
     assert scalar_close(obj[2].item(), co.item(), c3.item() - co.item()), (c, "reconstErr", obj[2].item(), co.item(), c3.item())
+    measured = {}
     for k, a, b, b32 in zip(SG, g_obj, go, g3):
         assert torch.isfinite(a).all(), (c, k)
         if float(b.norm()) == 0.0:      # every image of the case without a ground-truth env AND no live render pixel: nothing to compare
             assert float(a.abs().max()) == 0.0
             continue
-        bound = tol2(rel_l2(b32, b)) if q > 1 else max(tol2(rel_l2(b32, b)), 2.0 * E_REF_SPEC_RATIO1)
+        measured[k] = (rel_l2(a, b), rel_l2(b32, b))
+        bound = max(tol2(rel_l2(b32, b)), 2.0 * E_REF_SPEC_RATIO1) if q == 1 and k in RATIO1_FLOOR else tol2(rel_l2(b32, b))
         assert rel_l2(a, b) <= bound, (c, "objective g_" + k, rel_l2(a, b), rel_l2(b32, b))
+    print(f"\ncase {c['case']} q={q} F0={F0}: objective gradients (error, fp32 oracle's own):", {k: f"{v[0]:.2e} ({v[1]:.2e})" for k, v in measured.items()})
     with torch.no_grad():               # the forward-only route (no gradient kernel) returns the same values
         ng = sgr.light_objective(layer, x["albedo"], x["normal"], x["rough"], x["axis"], x["lamb"], x["weight"], x["im"], x["seg"], x["env_gt"], ind.cuda(), 1.0, 10.0)
     assert abs(ng[0].item() - obj[0].item()) <= 2e-6 * abs(obj[0].item()), (c, ng[0].item(), obj[0].item())

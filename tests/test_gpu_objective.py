@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import layer_kwargs, rel_l2, scalar_close
+from conftest import layer_kwargs, rel_l2, scalar_close, tol2
 
 pytestmark = pytest.mark.gpu
 
@@ -91,7 +91,7 @@ def test_light_objective_vs_oracle(sgr, bn, imH, imW, R, C, K, benign, eh, ew):
         ind[1] = 0.0
     ren_w, rec_w, offset = 0.7, 3.0, 1.0
     tot_o, rerr_o, cerr_o, g_o = _oracle_objective(inp, ind, R, C, eh, ew, fov, F0, ren_w, rec_w, offset)
-    _, rerr_32, cerr_32, _ = _oracle_objective(inp, ind, R, C, eh, ew, fov, F0, ren_w, rec_w, offset, torch.float32)
+    _, rerr_32, cerr_32, g_32 = _oracle_objective(inp, ind, R, C, eh, ew, fov, F0, ren_w, rec_w, offset, torch.float32)
     n32 = (abs(rerr_32 - rerr_o), abs(cerr_32 - cerr_o))      # the fp32 oracle's own error on the two reported values
 
     dev = {k: v.cuda() for k, v in inp.items()}
@@ -105,8 +105,12 @@ def test_light_objective_vs_oracle(sgr, bn, imH, imW, R, C, K, benign, eh, ew):
     assert scalar_close(cerr.item(), cerr_o, n32[1]), (cerr.item(), cerr_o, n32)
     assert scalar_close(obj.item(), tot_o, ren_w * n32[0] + rec_w * n32[1]), (obj.item(), tot_o)
     grads = torch.autograd.grad(2.0 * obj, [dev["axis"], dev["lamb"], dev["weight"]])     # cotangent != 1
-    for k, g, go in zip(("axis", "lamb", "weight"), grads, g_o):
-        assert rel_l2(g.cpu(), 2.0 * go) < 2e-4, (k, rel_l2(g.cpu(), 2.0 * go))
+    for k, g, go, g32 in zip(("axis", "lamb", "weight"), grads, g_o, g_32):
+        # max(2 e32, 1e-4), e32 = the fp32 oracle's own gradient error on these inputs; the flat 2e-4 of rounds 2-6 stays as a cap
+        e32 = rel_l2(g32, go)
+        bound = tol2(e32)
+        assert bound <= 2e-4, (k, "yardstick-derived bound above the cap", bound, e32)
+        assert rel_l2(g.cpu(), 2.0 * go) <= bound, (k, rel_l2(g.cpu(), 2.0 * go), e32)
 
     # unfused HIP path on the same inputs
     env, d, s = layer.forwardSG(dev["albedo"], dev["normal"], dev["rough"], dev["axis"], dev["lamb"], dev["weight"], need_env=True)
@@ -216,7 +220,6 @@ def test_light_objective_from_decoder_outputs(sgr, bn, imH, imW, R, C, K, eh, ew
     """``light_objective(decoder_outputs=True)``: values and gradients w.r.t. the decoders' last-convolution outputs against
     the fp64 oracle (heads of models.py:336-346 + wrapperBRDFLight.py:167-207) within twice the fp32 oracle's own noise, and
     against the two-step HIP route (standalone heads pass, then the objective)."""
-    from conftest import tol2
     from oracle import sg_oracle as O
     fov, F0, ren_w, rec_w = 57.0, 0.05, 1.0, 10.0
     inp = O.synthetic_inputs(bn, imH, imW, R, C, K, eh, ew, seed=300 + K, benign=True)

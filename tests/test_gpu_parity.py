@@ -243,8 +243,8 @@ def test_shapes_vs_oracle(sgr, shape):
 
 
 def test_full_size_properties(sgr):
-    """BASELINE config 2 (bn=16, 240x320 -> 120x160, K=12, 8x16): size-independent properties plus an
-    oracle check of two of the sixteen images."""
+    """BASELINE config 2 (bn=16, 240x320 -> 120x160, K=12, 8x16): size-independent properties, and the fused and the two-call forward
+    of all sixteen images against the fp64 oracle."""
     from oracle import sg_oracle as O
     bn, imH, imW, R, C, K = 16, 240, 320, 120, 160, 12
     inp = O.synthetic_inputs(bn, imH, imW, R, C, K, seed=20202)
@@ -266,7 +266,25 @@ def test_full_size_properties(sgr):
     _, d3, s3 = layer.forwardSG(x["albedo"], x["normal"], x["rough"], x["axis"], x["lamb"], x["weight"], need_env=False)
     assert rel_l2(d3.cpu(), d.cpu()) < 1e-6 and rel_l2(s3.cpu(), s.cpu()) < 1e-6
     d4, s4 = layer.forwardEnv(x["albedo"], x["normal"], x["rough"], env)
-    assert rel_l2(d4.cpu(), d.cpu()) < 1e-5 and rel_l2(s4.cpu(), s.cpu()) < 2e-4
+    assert rel_l2(d4.cpu(), d.cpu()) < 1e-5
+    # both routes against the fp64 oracle (forward only, image by image on the GPU) within max(2 e32, 1e-4), e32 = the fp32 oracle's own
+    # error on these images; the flat 2e-4 between the two routes that rounds 2-6 asserted stays as a cap on that bound
+    ref = {t: {"diffuse": [], "spec": []} for t in (torch.float64, torch.float32)}
+    with torch.no_grad():
+        for b in range(bn):
+            for t in ref:
+                _, do, so = O.render_from_sg(*[inp[k][b:b + 1].to("cuda", t) for k in NAMES])
+                ref[t]["diffuse"].append(do)
+                ref[t]["spec"].append(so)
+    for k, fused, two_call in (("diffuse", d, d4), ("spec", s, s4)):
+        r64, r32 = torch.cat(ref[torch.float64][k]), torch.cat(ref[torch.float32][k])
+        e32 = rel_l2(r32, r64)
+        bound = tol2(e32)
+        assert bound <= 2e-4, (k, "yardstick-derived bound above the cap", bound, e32)
+        assert rel_l2(fused, r64) <= bound, (k, "fused", rel_l2(fused, r64), e32)
+        assert rel_l2(two_call, r64) <= bound, (k, "two-call", rel_l2(two_call, r64), e32)
+        print(f"config 2 {k}: fused {rel_l2(fused, r64):.2e}, two-call {rel_l2(two_call, r64):.2e} vs fp64 (fp32 oracle's own {e32:.2e}); "
+              f"between the routes {rel_l2(two_call, fused):.2e}", end="; ")
     # linearity in the (post-tan) weights, exact for a power-of-two scale
     o2e = sgr.output2env(K)
     lam_t = torch.tan(np.pi / 2 * (0.999 * x["lamb"]))
@@ -406,8 +424,19 @@ def test_sharp_lobes_sharpness_gradient(sgr, lo):
     T t per direction -- a difference that cancels by ~1 / mean|a . l - 1|, i.e. worst for the sharpest lobes.  Here EVERY lobe is sharp
     (decoder output in [lo, 1): lam = tan(pi/2 0.999 x) from 6.3 or 64 up to the pre-map's maximum 636), fused layer and fused objective,
     against the fp64 oracle at the usual bound max(2 e_ref, 1e-4) with e_ref = the fp32 oracle's own error on these inputs."""
+    _sharp_lobes(sgr, lo, 12, 8, 16)
+
+
+@pytest.mark.parametrize("lo", [0.9, 0.99], ids=["lam_6_to_636", "lam_64_to_636"])
+def test_sharp_lobes_sharpness_gradient_16x32_k24(sgr, lo):
+    """The same on config 5's kernels (24 lobes, 16x32 directions): directions about twice as close to a sharp axis, so the cancellation of
+    a . S - w . q is larger there."""
+    _sharp_lobes(sgr, lo, 24, 16, 32)
+
+
+def _sharp_lobes(sgr, lo, K, eh, ew):
     from oracle import sg_oracle as O
-    bn, imH, imW, R, C, K, eh, ew = 2, 24, 32, 12, 16, 12, 8, 16
+    bn, imH, imW, R, C = 2, 24, 32, 12, 16
     inp = O.synthetic_inputs(bn, imH, imW, R, C, K, eh, ew, seed=606)
     g0 = torch.Generator().manual_seed(17)
     inp["lamb"] = lo + (0.99999 - lo) * torch.rand(inp["lamb"].shape, generator=g0)
@@ -427,7 +456,7 @@ def test_sharp_lobes_sharpness_gradient(sgr, lo):
     for k, a, b in zip(("axis", "lamb", "weight"), gr, go):
         assert torch.isfinite(a).all(), k
         assert rel_l2(a.cpu(), b) <= tol2(e32["g_" + k]), ("layer", k, rel_l2(a.cpu(), b), e32["g_" + k])
-    print(f"sharp lobes (x >= {lo}): layer sharpness-gradient error {rel_l2(gr[1].cpu(), go[1]):.2e} (fp32 oracle's own {e32['g_lamb']:.2e})", end=" ")
+    print(f"sharp lobes (x >= {lo}, K={K}, {eh}x{ew}): layer sharpness-gradient error {rel_l2(gr[1].cpu(), go[1]):.2e} (fp32 oracle's own {e32['g_lamb']:.2e})", end=" ")
     ind = torch.ones(bn, 1, 1, 1)
     obj = sgr.light_objective(layer, x["albedo"], x["normal"], x["rough"], x["axis"], x["lamb"], x["weight"], x["im"], x["seg"],
                               x["env_gt"], ind.cuda(), 1.0, 10.0)

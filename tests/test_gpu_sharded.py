@@ -2,7 +2,8 @@
 
 Two ranks (torch.multiprocessing spawn, gloo backend -- it moves CUDA tensors through the host, so one GPU is enough)
 each run the render layer, ``sgr.render_loss(..., group)`` and ``sgr.light_objective(..., group)`` -- also with
-``decoder_outputs=True`` and at config-5 shapes (24 lobes, 16x32 directions, ragged 16-pixel tiles) -- on their half of the batch; the losses and the SG gradients must equal those of the single-process full batch
+``decoder_outputs=True``, at config-5 shapes (24 lobes, 16x32 directions, ragged 16-pixel tiles) and at config-2 size (8 images of
+240x320) -- on their half of the batch; the losses and the SG gradients must equal those of the single-process full batch
 (wrapperBRDFLight.py:192,205-207: the normaliser is the batch-global mask sum).  The 8-GPU RCCL run itself belongs to the
 driver (bench.py --gpus N)."""
 import os
@@ -21,6 +22,9 @@ CASES = {
     "k12_8x16_decoder_outputs": dict(bn=4, imH=24, imW=32, R=12, C=16, K=12, eh=8, ew=16, heads=True),
     "k24_16x32_ragged": dict(bn=4, imH=10, imW=14, R=5, C=7, K=24, eh=16, ew=32, heads=False),
     "k24_16x32_decoder_outputs": dict(bn=4, imH=10, imW=14, R=5, C=7, K=24, eh=16, ew=32, heads=True),
+    # round 7: the stage route AT SIZE -- 8 images of config 2 (240x320 -> 120x160), 600 partial tiles per image folded on each rank
+    "cfg2_8img": dict(bn=8, imH=240, imW=320, R=120, C=160, K=12, eh=8, ew=16, heads=False),
+    "cfg2_8img_decoder_outputs": dict(bn=8, imH=240, imW=320, R=120, C=160, K=12, eh=8, ew=16, heads=True),
 }
 NAMES = ("albedo", "normal", "rough", "axis", "lamb", "weight")
 SG = ("axis", "lamb", "weight")
@@ -36,7 +40,9 @@ def _inputs(c):
     from oracle import sg_oracle as O      # checker-side input generator only
     inp = O.synthetic_inputs(c["bn"], c["imH"], c["imW"], c["R"], c["C"], c["K"], c["eh"], c["ew"], seed=4242)
     inp["seg"][1] = 0.0                    # uneven denominators across the shards
-    inp["ind"] = torch.tensor([1.0, 1.0, 0.0, 1.0]).reshape(c["bn"], 1, 1, 1)
+    ind = torch.ones(c["bn"])
+    ind[2::4] = 0.0                        # [1, 1, 0, 1] per four images
+    inp["ind"] = ind.reshape(c["bn"], 1, 1, 1)
     if c["heads"]:                         # the three light decoders' last-convolution outputs (models.py:336-346 come after them)
         g = torch.Generator().manual_seed(99)
         bn, K, R, C = c["bn"], c["K"], c["R"], c["C"]
@@ -90,13 +96,17 @@ def test_two_ranks_on_one_gpu_match_the_full_batch(case):
     mp.spawn(_worker, args=(world, _free_port(), case, out), nprocs=world, join=True)
     full = _run(case, slice(0, CASES[case]["bn"]), None)
     per = CASES[case]["bn"] // world
+    worst_v = worst_g = 0.0
     for r in range(world):
         o = out[r]
         for k in ("err", "rec", "obj", "obj_err", "obj_rec"):
             assert abs(o[k] - full[k]) <= 2e-6 * abs(full[k]), (case, r, k, o[k], full[k])
+            worst_v = max(worst_v, abs(o[k] - full[k]) / abs(full[k]))
         for tag in ("g1", "g2"):
             for name, a, b in zip(SG, o[tag], full[tag]):
                 b = b[r * per:(r + 1) * per]
                 assert torch.isfinite(a).all()
                 rel = ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
                 assert rel < 5e-6, (case, r, tag, name, rel)
+                worst_g = max(worst_g, rel)
+    print(f"\n{case}: two ranks vs the full batch, worst value {worst_v:.2e} (bound 2e-6), worst gradient {worst_g:.2e} (bound 5e-6)")

@@ -103,3 +103,32 @@ def test_broadcast_restatement_matches_looped_oracle():
         outs.append((env, d, s) + tuple(g))
     for a, b in zip(*outs):
         assert rel_l2(a.detach(), b.detach()) < 1e-12
+
+
+def test_oracle_fp64_objective_at_size_matches_g12():
+    """Fixture g12 (oracle/make_golden_fullsize.py): the reference's training objective on one image of config 2.  The inputs regenerate
+    from the seed (checksums of the six maps and of im / seg / env_gt must hold), and the fp64 oracle reproduces the reference's fp64
+    loss values, numerator / denominator, rendered image and the strided SG gradients of renderErr + 10 reconstErr to round-off."""
+    import os
+    from conftest import GOLDEN_DIR
+    z = np.load(os.path.join(GOLDEN_DIR, "g12_cfg2_objective.npz"))
+    cfg = {k: v for k, v in zip(z["cfg_keys"].tolist(), z["cfg_vals"].tolist())}
+    bn, imH, imW, R, C, K, eh, ew = (int(cfg[k]) for k in ("bn", "imH", "imW", "R", "C", "K", "eh", "ew"))
+    inp = O.synthetic_inputs_np(bn, imH, imW, R, C, K, eh, ew, seed=int(cfg["seed"]))
+    assert np.allclose([inp[k].double().sum().item() for k in NAMES], z["in_checksums"], rtol=1e-12)
+    assert np.allclose([inp[k].double().sum().item() for k in ("im", "seg", "env_gt")], z["in_checksums_loss"], rtol=1e-12)
+    x = {k: v.double() for k, v in inp.items()}
+    for k in ("axis", "lamb", "weight"):
+        x[k].requires_grad_(True)
+    env, d, s = O.render_from_sg(x["albedo"], x["normal"], x["rough"], x["axis"], x["lamb"], x["weight"], eh, ew, cfg["fov"], cfg["F0"])
+    rerr, ren, num, den = O.render_loss(d, s, x["im"], x["seg"], R, C)
+    cerr, _, _, _ = O.recon_loss(env, x["env_gt"], x["seg"], torch.ones(bn, 1, 1, 1, dtype=torch.float64), R, C)
+    grads = torch.autograd.grad(rerr + 10.0 * cerr, [x[k] for k in ("axis", "lamb", "weight")])
+    for k, v in (("render_err", rerr), ("recon_err", cerr), ("render_num", num), ("render_den", den)):
+        assert abs(v.item() - float(z["ref64_" + k][0])) <= 1e-10 * abs(float(z["ref64_" + k][0])), (k, v.item(), z["ref64_" + k])
+    assert rel_l2(ren.detach(), z["ref64_rendered"]) < 1e-7        # stored rounded to fp32
+    st = int(z["stride_sg"][0])
+    for k, g in zip(("axis", "lamb", "weight"), grads):
+        assert rel_l2(g[..., ::st, ::st], z["ref64_gtot_" + k]) < 1e-7, k
+        n = float(z[f"ref64_gtot_{k}_norm"][0])
+        assert abs(g.norm().item() - n) <= 1e-10 * n, k
