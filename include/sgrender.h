@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SGR_ABI_VERSION 5
+#define SGR_ABI_VERSION 6
 #define SGR_MAX_LOBES 32
 
 #define SGR_OK 0
@@ -322,6 +322,30 @@ int sgr_fused_bwd_recon_total(const float* albedo, const float* normal, const fl
                               int bn, int K, int R, int C, int eh, int ew, int imH, int imW, float F0, int premap,
                               float offset, float rec_weight, const float* render_err, float ren_weight,
                               float* objective, float* recon_err, float* applied2, void* stream);
+
+/* ABI 6: sgr_fused_bwd_recon / sgr_fused_bwd_recon_total that also return the objective's gradients w.r.t. the BRDF maps:
+ * g_albedo [bn,3,imH,imW], g_normal [bn,3,imH,imW], g_rough [bn,1,imH,imW] (imH x imW = 1x or 2x the env grid, the 2x2 pooling's adjoint
+ * applied).  They are ren_weight x d renderErr / d map: the reconstruction term does not depend on the maps, so they come from the render
+ * layer's BRDF backward from the SG lobes (sgr_render_bwd_brdf with env = NULL) driven by g_diffuse / g_spec, launched after the objective's
+ * pass.  The three are given together (with the SG gradient trio) or all NULL, which is the plain entry point (SGR_ERR_BAD_ARG otherwise);
+ * premap 3 with them is SGR_ERR_UNSUPPORTED (activate the decoder outputs with sgr_light_heads_fwd and call sgr_render_bwd_brdf). */
+int sgr_fused_bwd_recon_brdf(const float* albedo, const float* normal, const float* rough, const float* axis,
+                             const float* lamb, const float* weight, const float* dirs, const float* view,
+                             const float* env_gt, const float* mask, const float* coef, const float* den_global,
+                             const float* g_diffuse, const float* g_spec,
+                             float* g_axis, float* g_lamb, float* g_weight,
+                             float* g_albedo /* nullable trio */, float* g_normal, float* g_rough,
+                             float* parts, float* workspace, int bn, int K, int R, int C, int eh, int ew, int imH, int imW,
+                             float F0, int premap, float offset, float rec_weight, void* stream);
+int sgr_fused_bwd_recon_total_brdf(const float* albedo, const float* normal, const float* rough, const float* axis,
+                                   const float* lamb, const float* weight, const float* dirs, const float* view,
+                                   const float* env_gt, const float* mask, const float* coef,
+                                   const float* g_diffuse, const float* g_spec,
+                                   float* g_axis, float* g_lamb, float* g_weight,
+                                   float* g_albedo /* nullable trio */, float* g_normal, float* g_rough,
+                                   float* parts, float* workspace, int bn, int K, int R, int C, int eh, int ew, int imH, int imW,
+                                   float F0, int premap, float offset, float rec_weight, const float* render_err, float ren_weight,
+                                   float* objective, float* recon_err, float* applied2, void* stream);
 
 /* Tail of the light objective on the device: *recon_err = parts_e[0] / max(parts_e[1], 1e-5) / divisor_e (divisor 3 * eh * ew,
  * wrapperBRDFLight.py:179-188), *objective = ren_w * *render_err + rec_w * *recon_err (trainLight.py:237).  parts_e = (numerator,

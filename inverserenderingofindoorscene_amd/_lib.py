@@ -18,7 +18,7 @@ from ctypes import c_char_p, c_float, c_int, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGR_LIB", os.path.join(_HERE, "libsgrender.so"))
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class SgrenderUnavailable(RuntimeError):
@@ -77,6 +77,8 @@ SIGNATURES = {
     "sgr_rescale_inplace_flip": ([_P, _P, _I, _P, _P, _I, _P], c_int),
     "sgr_fused_bwd_recon": ([_P] * 19 + [_I] * 8 + [_F, _I, _F, _F, _P], c_int),
     "sgr_fused_bwd_recon_total": ([_P] * 18 + [_I] * 8 + [_F, _I, _F, _F, _P, _F, _P, _P, _P, _P], c_int),
+    "sgr_fused_bwd_recon_brdf": ([_P] * 22 + [_I] * 8 + [_F, _I, _F, _F, _P], c_int),
+    "sgr_fused_bwd_recon_total_brdf": ([_P] * 21 + [_I] * 8 + [_F, _I, _F, _F, _P, _F, _P, _P, _P, _P], c_int),
     "sgr_glue_workspace_floats": ([_I], c_int),
     "sgr_light_albedo_scale": ([_P] * 7 + [ctypes.c_longlong, ctypes.c_longlong, _P], c_int),
     "sgr_light_input_fwd": ([_P] * 9 + [_I] * 5 + [_P], c_int),

@@ -701,6 +701,58 @@ extern "C" int sgr_fused_bwd_recon_total(const float* albedo, const float* norma
                               g_lamb, g_weight, parts, workspace, bn, K, R, C, eh, ew, imH, imW, F0, premap, offset, rec_weight, tail, stream);
 }
 
+// ABI 6: the same two entry points with the objective's gradients w.r.t. the BRDF maps as well.  The maps enter the objective through the
+// render term alone, so d objective / d map is the render layer's BRDF adjoint driven by the cotangents g_diffuse / g_spec the caller
+// already holds (ren_weight x d renderErr / d{diffuse, spec}): sgr_render_bwd_brdf from the SG lobes, after the objective's pass.  Measured
+// against the adjoint fused into sg_bwd_recon_pk_kernel (profiles/r07a_objective_brdf_ab.txt, config 2): the fused form had to run one wave
+// per SIMD and cost 282 us over the SG-only objective, this second pass ~210 us.  The three outputs come together or not at all.
+static int brdf_outputs_check(const float* g_axis, float* g_albedo, float* g_normal, float* g_rough, int premap, const char* who) {
+  SGR_REQUIRE((g_albedo && g_normal && g_rough) || (!g_albedo && !g_normal && !g_rough), who);
+  SGR_REQUIRE(!g_albedo || g_axis, who);
+  SGR_SUPPORTED(!g_albedo || premap != 3, "sgr_fused_bwd_recon_brdf: premap 3 (decoder outputs): activate them with sgr_light_heads_fwd and pass premap 1");
+  return 0;
+}
+static int brdf_after(int rc, const float* g_diffuse, const float* g_spec, const float* albedo, const float* normal, const float* rough,
+                      const float* axis, const float* lamb, const float* weight, const float* dirs, const float* view, float* g_albedo,
+                      float* g_normal, float* g_rough, int bn, int K, int R, int C, int eh, int ew, int imH, int imW, float F0, int premap,
+                      void* stream) {
+  if (rc || !g_albedo) return rc;
+  return sgr_render_bwd_brdf(g_diffuse, g_spec, albedo, normal, rough, nullptr, axis, lamb, weight, dirs, view, g_albedo, g_normal, g_rough, bn,
+                             K, R, C, eh, ew, imH, imW, F0, premap, stream);
+}
+extern "C" int sgr_fused_bwd_recon_brdf(const float* albedo, const float* normal, const float* rough, const float* axis, const float* lamb,
+                                        const float* weight, const float* dirs, const float* view, const float* env_gt, const float* mask,
+                                        const float* coef, const float* den_global, const float* g_diffuse, const float* g_spec,
+                                        float* g_axis, float* g_lamb, float* g_weight, float* g_albedo, float* g_normal, float* g_rough,
+                                        float* parts, float* workspace, int bn, int K, int R, int C, int eh, int ew, int imH, int imW, float F0,
+                                        int premap, float offset, float rec_weight, void* stream) {
+  if (int rc = brdf_outputs_check(g_axis, g_albedo, g_normal, g_rough, premap,
+                                  "sgr_fused_bwd_recon_brdf: g_albedo / g_normal / g_rough come all three (with the SG gradients) or not at all"))
+    return rc;
+  const int rc = fused_bwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, mask, coef, den_global, g_diffuse, g_spec,
+                                      g_axis, g_lamb, g_weight, parts, workspace, bn, K, R, C, eh, ew, imH, imW, F0, premap, offset, rec_weight,
+                                      ObjectiveTail{}, stream);
+  return brdf_after(rc, g_diffuse, g_spec, albedo, normal, rough, axis, lamb, weight, dirs, view, g_albedo, g_normal, g_rough, bn, K, R, C, eh, ew,
+                    imH, imW, F0, premap, stream);
+}
+extern "C" int sgr_fused_bwd_recon_total_brdf(const float* albedo, const float* normal, const float* rough, const float* axis,
+                                              const float* lamb, const float* weight, const float* dirs, const float* view, const float* env_gt,
+                                              const float* mask, const float* coef, const float* g_diffuse, const float* g_spec, float* g_axis,
+                                              float* g_lamb, float* g_weight, float* g_albedo, float* g_normal, float* g_rough, float* parts,
+                                              float* workspace, int bn, int K, int R, int C, int eh, int ew, int imH, int imW, float F0, int premap,
+                                              float offset, float rec_weight, const float* render_err, float ren_weight, float* objective,
+                                              float* recon_err, float* applied2, void* stream) {
+  SGR_REQUIRE(render_err && objective && recon_err, "sgr_fused_bwd_recon_total_brdf: NULL scalar");
+  if (int rc = brdf_outputs_check(g_axis, g_albedo, g_normal, g_rough, premap,
+                                  "sgr_fused_bwd_recon_total_brdf: g_albedo / g_normal / g_rough come all three (with the SG gradients) or not at all"))
+    return rc;
+  ObjectiveTail tail{render_err, ren_weight, rec_weight, 3.0f * (float)(eh * ew), objective, recon_err, applied2};
+  const int rc = fused_bwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, mask, coef, nullptr, g_diffuse, g_spec, g_axis,
+                                      g_lamb, g_weight, parts, workspace, bn, K, R, C, eh, ew, imH, imW, F0, premap, offset, rec_weight, tail, stream);
+  return brdf_after(rc, g_diffuse, g_spec, albedo, normal, rough, axis, lamb, weight, dirs, view, g_albedo, g_normal, g_rough, bn, K, R, C, eh, ew,
+                    imH, imW, F0, premap, stream);
+}
+
 // Cotangent scaling for gradients that were produced ahead of the backward call (sgr.light_objective):
 // every x[i] (i = 0..count-1, n[i] floats, 16-byte aligned) is multiplied in place by scale / *applied, then
 // *applied = scale; nothing is touched when the two are equal.  All on the stream, no host sync.

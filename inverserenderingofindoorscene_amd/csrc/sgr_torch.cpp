@@ -73,7 +73,8 @@ using Cam = at::ArrayRef<double>;
   X(sgr_lsregress_coef) X(sgr_lsregress_diffspec_coef) X(sgr_sg_shading) X(sgr_recon_workspace_floats) X(sgr_recon_loss_fwd)     \
   X(sgr_recon_loss_bwd) X(sgr_fused_recon_supported) X(sgr_heads_prologue_supported) X(sgr_fused_recon_workspace_floats)         \
   X(sgr_fused_fwd_recon_seg) X(sgr_light_objective_fwd) X(sgr_light_heads_fwd) X(sgr_light_heads_bwd) X(sgr_rescale_inplace_flip) X(sgr_fused_bwd_recon)    \
-  X(sgr_fused_bwd_recon_total) X(sgr_glue_workspace_floats) X(sgr_light_albedo_scale) X(sgr_light_input_fwd)
+  X(sgr_fused_bwd_recon_total) X(sgr_glue_workspace_floats) X(sgr_light_albedo_scale) X(sgr_light_input_fwd)                  \
+  X(sgr_fused_bwd_recon_brdf) X(sgr_fused_bwd_recon_total_brdf)
 
 struct Api {
 #define SGR_DECL(name) decltype(&::name) name = nullptr;
@@ -1231,6 +1232,224 @@ T2 light_objective_stage3_meta(const Tensor& render_err, const Tensor&, const Te
   return {at::empty({}, render_err.options()), at::empty({}, render_err.options())};
 }
 
+// ---- the objective with gradients w.r.t. the BRDF maps as well (light_objective(..., brdf_grads=True)) ----------------------------
+// The same launches as light_objective_fwdbwd / light_objective_stage2, then the render layer's BRDF backward from the SG lobes driven by the
+// render cotangents those already hold (sgr_fused_bwd_recon_total_brdf / sgr_fused_bwd_recon_brdf); a map that is not asked for gets no
+// output (an empty tensor).
+// Six precomputed gradients: the SG trio and the three maps, scaled by the incoming cotangent exactly like the trio (two launches of
+// sgr_rescale_inplace_flip with the same parity: each reads applied2[parity] and writes the new factor to the other slot).
+void rescale_grads6_cuda(Tensor& g_axis, Tensor& g_lamb, Tensor& g_weight, Tensor& g_albedo, Tensor& g_normal, Tensor& g_rough, const Tensor& scale,
+                         Tensor& applied, int64_t parity) {
+  const auto dev = require_hip({&g_axis, &g_lamb, &g_weight, &scale, &applied});
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(g_axis.is_contiguous() && g_lamb.is_contiguous() && g_weight.is_contiguous() && applied.numel() == 2 && scale.numel() == 1, "sgrender: rescale_grads6_ arguments");
+  const Tensor sc = scale.contiguous();
+  float* xs[3] = {g_axis.data_ptr<float>(), g_lamb.data_ptr<float>(), g_weight.data_ptr<float>()};
+  long long ns[3] = {(long long)g_axis.numel(), (long long)g_lamb.numel(), (long long)g_weight.numel()};
+  ok(api().sgr_rescale_inplace_flip(xs, ns, 3, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
+  int nb = 0;
+  for (Tensor* t : {&g_albedo, &g_normal, &g_rough}) {
+    if (!present(*t)) continue;
+    TORCH_CHECK(t->is_contiguous() && t->device() == dev, "sgrender: rescale_grads6_ arguments");
+    xs[nb] = t->data_ptr<float>();
+    ns[nb++] = (long long)t->numel();
+  }
+  if (nb) ok(api().sgr_rescale_inplace_flip(xs, ns, nb, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
+}
+void rescale_grads6_meta(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t) {}
+
+struct PrecomputedGrads6Fn : public torch::autograd::Function<PrecomputedGrads6Fn> {
+  // inputs: value, axis, lamb, weight, albedo, normal, rough, then their six gradients (a map's empty when not asked for) and `applied`
+  static Tensor forward(AutogradContext* ctx, const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& albedo,
+                        const Tensor& normal, const Tensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight, const Tensor& g_albedo,
+                        const Tensor& g_normal, const Tensor& g_rough, const Tensor& applied) {
+    ctx->save_for_backward({g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied});
+    ctx->saved_data["parity"] = (int64_t)0;
+    ctx->saved_data["handed_out"] = false;
+    ctx->set_materialize_grads(false);
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return value.alias();
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list g) {
+    variable_list out(14);
+    if (!g[0].defined()) return out;
+    const auto saved = ctx->get_saved_variables();
+    Tensor gs[6] = {saved[0], saved[1], saved[2], saved[3], saved[4], saved[5]};
+    Tensor applied = saved[6];
+    const int64_t parity = ctx->saved_data["parity"].toInt();
+    if (ctx->saved_data["handed_out"].toBool()) {      // a second backward through this node: as PrecomputedGradsFn
+      TORCH_CHECK(applied[parity].item<float>() != 0.0f, "sgrender: light_objective was first back-propagated with a zero cotangent; its stored "
+                  "gradients are gone -- re-evaluate the objective instead of reusing the graph");
+      const Tensor f = g[0].detach() / applied[parity];
+      for (int i = 0; i < 6; ++i)
+        if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i] * f;
+      return out;
+    }
+    ctx->saved_data["handed_out"] = true;
+    static auto op = find_op<void(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t)>("sgrender::rescale_grads6_");
+    op.call(gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], g[0].detach().to(at::kFloat).reshape({1}), applied, parity);
+    ctx->saved_data["parity"] = (int64_t)(1 - parity);
+    for (int i = 0; i < 6; ++i)
+      if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i];
+    return out;
+  }
+};
+Tensor attach_grads6_backend(const Tensor& value, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                             const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
+  return value.clone();
+}
+Tensor attach_grads6_autograd(const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& albedo, const Tensor& normal,
+                              const Tensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight, const Tensor& g_albedo, const Tensor& g_normal,
+                              const Tensor& g_rough, const Tensor& applied) {
+  return PrecomputedGrads6Fn::apply(value, axis, lamb, weight, albedo, normal, rough, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied);
+}
+
+// Decoder outputs (heads): the BRDF backward needs the activated SG parameters -- sgr_light_heads_fwd into temporaries, then the layer's
+// BRDF backward from them (premap 1) driven by the objective's render cotangents; the SG pass itself keeps the heads as its prologue.
+void heads_brdf_pass(const Tensor& ax, const Tensor& la, const Tensor& we, const Tensor& a, const Tensor& n, const Tensor& r, const Tensor& g_d,
+                     const Tensor& g_s, const Tensor& dirs, const Tensor& view, Tensor& g_alb, Tensor& g_nrm, Tensor& g_rgh, int64_t bn, int64_t K,
+                     int64_t R, int64_t C, int64_t eh, int64_t ew, int64_t h, int64_t w, double F0, void* st) {
+  const Api& A = api();
+  const auto o = a.options();
+  Tensor axis = at::empty({bn, K, 3, R, C}, o), lamb = at::empty({bn, K, R, C}, o), weight = at::empty({bn, 3 * K, R, C}, o);
+  ok(A.sgr_light_heads_fwd(rp(ax), rp(la), rp(we), wp(axis), wp(lamb), wp(weight), nullptr, (int)bn, (int)K, (int)R, (int)C, st), "sgr_light_heads_fwd");
+  ok(A.sgr_render_bwd_brdf(rp(g_d), rp(g_s), rp(a), rp(n), rp(r), nullptr, rp(axis), rp(lamb), rp(weight), rp(dirs), rp(view), wp(g_alb), wp(g_nrm),
+                           wp(g_rgh), (int)bn, (int)K, (int)R, (int)C, (int)eh, (int)ew, (int)h, (int)w, (float)F0, 1, st),
+     "sgr_render_bwd_brdf");
+}
+
+// light_objective_brdf_fwdbwd(...) -> (objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied)
+// light_objective_fwdbwd(need_grad = True) followed by the BRDF maps' gradients (sgr_fused_bwd_recon_total_brdf: the objective's pass, then
+// the layer's BRDF backward from the SG lobes); g_albedo / g_normal / g_rough at the maps' resolution (1x or 2x the env grid), empty where
+// not wanted (the C ABI writes the three together)
+T12 light_objective_brdf_fwdbwd_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
+                                     const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0,
+                                     Cam cam, double ren_w, double rec_w, double offset, bool heads, bool handoff, bool want_albedo, bool want_normal, bool want_rough) {
+  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind});
+  const c10::DeviceGuard guard(dev);
+  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
+  const Tensor i = im.contiguous(), sg = seg.contiguous(), gt = env_gt.contiguous(), ind = env_ind.contiguous().reshape({-1});
+  const auto d = check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew);
+  const auto o = a.options();
+  const Api& A = api();
+  void* st = stream_of(dev);
+  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
+  Tensor diffuse = at::empty({d.bn, 3, d.R, d.C}, o), spec = at::empty({d.bn, 3, d.R, d.C}, o), im_s = at::empty({d.bn, 3, d.R, d.C}, o);
+  Tensor seg_s = at::empty({d.bn, 1, d.R, d.C}, o), rendered = at::empty({d.bn, 3, d.R, d.C}, o), mask = at::empty({d.bn, d.R * d.C}, o), coef = at::empty({d.bn}, o);
+  Tensor coef_ds = at::empty({d.bn, 2}, o), parts_r = at::empty({2}, o), parts_b = at::empty({2}, o), scale_r = at::empty({1}, o);
+  Tensor ws = at::empty({A.sgr_fused_recon_workspace_floats(bn, R, C)}, o), ws_r = loss_workspace(d.bn, a);
+  Tensor objective = at::empty({}, o), render_err = at::empty({}, o), recon_err = at::empty({}, o);
+  handoff = handoff && !heads;
+  const int pm = heads ? 3 : 1;
+  Tensor lam_t = handoff ? at::empty_like(la) : Tensor(), w_t = handoff ? at::empty_like(we) : Tensor();
+  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
+  Tensor g_axis = at::empty_like(ax), g_lamb = at::empty_like(la), g_weight = at::empty_like(we), applied = at::empty({2}, o);
+  Tensor g_d = at::empty_like(diffuse), g_s = at::empty_like(spec);
+  Tensor g_alb = at::empty_like(a), g_nrm = at::empty_like(n), g_rgh = at::empty_like(r);
+  ok(A.sgr_light_objective_fwd(rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), rp(gt), rp(i), rp(sg), rp(ind), wp(lam_t), wp(w_t), wp(diffuse), wp(spec),
+                               wp(mask), wp(coef), wp(im_s), wp(seg_s), wp(rendered), wp(coef_ds), wp(parts_r), render_err.data_ptr<float>(), wp(scale_r), (float)ren_w,
+                               wp(g_d), wp(g_s), wp(ws), wp(ws_r), bn, K, R, C, (int)eh, (int)ew, (int)d.imH, (int)d.imW, (int)d.h, (int)d.w, (float)F0, pm, st),
+     "sgr_light_objective_fwd");
+  ok(A.sgr_fused_bwd_recon_total_brdf(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
+                                      rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb), heads ? nullptr : wp(g_nrm),
+                                      heads ? nullptr : wp(g_rgh), wp(parts_b), wp(ws), bn, K, R, C, (int)eh, (int)ew, (int)d.h, (int)d.w, (float)F0,
+                                      handoff ? 2 : pm, (float)offset, (float)rec_w, rp(render_err), (float)ren_w, objective.data_ptr<float>(),
+                                      recon_err.data_ptr<float>(), wp(applied), st),
+     "sgr_fused_bwd_recon_brdf");
+  if (heads) heads_brdf_pass(ax, la, we, a, n, r, g_d, g_s, dirs, view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, d.h, d.w, F0, st);
+  return {objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, want_albedo ? g_alb : none_like(a), want_normal ? g_nrm : none_like(a),
+          want_rough ? g_rgh : none_like(a), applied};
+}
+T12 light_objective_brdf_fwdbwd_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
+                                     const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double, double, Cam, double,
+                                     double, double, bool, bool, bool want_albedo, bool want_normal, bool want_rough) {
+  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
+  const auto o = albedo.options();
+  auto g = [&](const Tensor& t, bool want) { return want ? at::empty(t.sizes(), o) : none_like(albedo); };
+  return {at::empty({}, o), at::empty({}, o), at::empty({}, o), at::empty({d.bn, 3, d.R, d.C}, o), at::empty({d.bn}, o), g(axis, true), g(lamb, true), g(weight, true),
+          g(albedo, want_albedo), g(normal, want_normal), g(rough, want_rough), at::empty({2}, o)};
+}
+using ObjBrdfSig = T12(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                       const Tensor&, int64_t, int64_t, double, double, Cam, double, double, double, bool, bool, bool, bool, bool);
+using ObjPlainSig = T5(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                       const Tensor&, int64_t, int64_t, double, double, Cam, double, double, double, bool, bool);
+
+// light_objective_brdf(...): light_objective differentiable w.r.t. the BRDF maps as well.  No grad-requiring map (or no grad mode): exactly
+// the light_objective operator (its launches, its node); the image-side inputs are still refused.
+T5 light_objective_brdf_autograd(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
+                                 const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam,
+                                 double ren_w, double rec_w, double offset, bool heads, bool handoff) {
+  const bool grad_mode = at::GradMode::is_enabled();
+  TORCH_CHECK(!(grad_mode && (im.requires_grad() || seg.requires_grad() || env_gt.requires_grad() || env_ind.requires_grad())),
+              "sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only (imBatch, segBRDFBatch, envmapsBatch and "
+              "envmapsIndBatch must not require grad)");
+  const bool wa = grad_mode && albedo.requires_grad(), wn = grad_mode && normal.requires_grad(), wr = grad_mode && rough.requires_grad();
+  if (!(wa || wn || wr)) {
+    static auto plain = find_op<ObjPlainSig>("sgrender::light_objective");
+    return plain.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff);
+  }
+  T12 o;
+  {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = find_op<ObjBrdfSig>("sgrender::light_objective_brdf_fwdbwd");
+    o = op.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff, wa, wn, wr);
+  }
+  Tensor objective = PrecomputedGrads6Fn::apply(std::get<0>(o), axis, lamb, weight, albedo, normal, rough, std::get<5>(o), std::get<6>(o), std::get<7>(o), std::get<8>(o),
+                                                std::get<9>(o), std::get<10>(o), std::get<11>(o));
+  return {objective, std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<4>(o)};
+}
+
+// stage 2 with the BRDF maps' gradients: (render_err, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, parts_b); always the gradient half
+using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+T8 light_objective_stage2_brdf_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
+                                    const Tensor& env_gt, const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
+                                    const Tensor& seg_s, const Tensor& coef_ds, const Tensor& sums, Tensor& ws, const Tensor& lam_t, const Tensor& w_t, int64_t eh,
+                                    int64_t ew, double fov, double F0, Cam cam, double ren_w, double rec_w, double offset, bool heads, bool want_albedo,
+                                    bool want_normal, bool want_rough) {
+  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws});
+  const c10::DeviceGuard guard(dev);
+  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
+  const Tensor gt = env_gt.contiguous();
+  const auto d = check_sg(ax, la, we);
+  const auto b = check_brdf(a, n, r);
+  TORCH_CHECK(sums.is_contiguous() && sums.numel() == 4 && mask.is_contiguous() && coef.is_contiguous() && diffuse.is_contiguous() && spec.is_contiguous() &&
+                  im_s.is_contiguous() && seg_s.is_contiguous() && coef_ds.is_contiguous() && ws.is_contiguous(), "sgrender: light_objective_stage2 takes stage 1's tensors as they are");
+  check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
+  TORCH_CHECK(gt.numel() == d.bn * 3 * d.R * d.C * eh * ew, "sgrender: light_objective_stage2: env_gt must be [bn,3,R,C,eh,ew], got ", gt.sizes());
+  const auto o = a.options();
+  const Api& A = api();
+  void* st = stream_of(dev);
+  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
+  const bool handoff = present(lam_t) && present(w_t);
+  Tensor render_err = at::empty({}, o), scale_r = at::empty({1}, o), parts_b = at::empty({2}, o);
+  const float* sp = sums.const_data_ptr<float>();
+  ok(A.sgr_loss_finalize(sp, render_err.data_ptr<float>(), wp(scale_r), 3.0f, st), "sgr_loss_finalize");
+  Tensor g_axis = at::empty_like(ax), g_lamb = at::empty_like(la), g_weight = at::empty_like(we), g_d = at::empty_like(diffuse), g_s = at::empty_like(spec);
+  Tensor g_alb = at::empty_like(a), g_nrm = at::empty_like(n), g_rgh = at::empty_like(r);
+  ok(A.sgr_render_loss_bwd_scaled(nullptr, (float)ren_w, rp(scale_r), rp(diffuse), rp(spec), rp(im_s), rp(seg_s), rp(coef_ds), wp(g_d), wp(g_s), bn, R, C, st),
+     "sgr_render_loss_bwd");
+  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
+  ok(A.sgr_fused_bwd_recon_brdf(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
+                                sp + 3 /* the global env-mask sum */, rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb),
+                                heads ? nullptr : wp(g_nrm), heads ? nullptr : wp(g_rgh), wp(parts_b), ws.mutable_data_ptr<float>(), bn, K, R, C, (int)eh, (int)ew,
+                                (int)b.h, (int)b.w, (float)F0, handoff ? 2 : (heads ? 3 : 1), (float)offset, (float)rec_w, st),
+     "sgr_fused_bwd_recon_brdf");
+  if (heads) heads_brdf_pass(ax, la, we, a, n, r, g_d, g_s, dirs, view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, b.h, b.w, F0, st);
+  return {render_err, g_axis, g_lamb, g_weight, want_albedo ? g_alb : none_like(a), want_normal ? g_nrm : none_like(a), want_rough ? g_rgh : none_like(a),
+          parts_b};
+}
+T8 light_objective_stage2_brdf_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
+                                    const Tensor&, const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
+                                    const Tensor& seg_s, const Tensor& coef_ds, const Tensor& sums, Tensor& ws, const Tensor&, const Tensor&, int64_t, int64_t, double,
+                                    double, Cam, double, double, double, bool, bool want_albedo, bool want_normal, bool want_rough) {
+  const auto d = check_sg(axis, lamb, weight);
+  check_brdf(albedo, normal, rough);
+  check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
+  const auto o = albedo.options();
+  auto g = [&](const Tensor& t, bool want) { return want ? at::empty(t.sizes(), o) : none_like(albedo); };
+  return {at::empty({}, o), g(axis, true), g(lamb, true), g(weight, true), g(albedo, want_albedo), g(normal, want_normal), g(rough, want_rough), at::empty({2}, o)};
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 void no_cpu_path(const c10::OperatorHandle&, torch::jit::Stack*) { TORCH_CHECK(false, kNoCpu); }
 
@@ -1381,6 +1600,21 @@ TORCH_LIBRARY(sgrender, m) {
         "Tensor diffuse, Tensor spec, Tensor im_s, Tensor seg_s, Tensor coef_ds, Tensor sums, Tensor(a!) ws, Tensor lam_t, Tensor w_t, int eh, int ew, float fov, float F0, "
         "float[] cam, float ren_w, float rec_w, float offset, bool heads, bool need_grad) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("light_objective_stage3(Tensor render_err, Tensor num_e, Tensor sums, float ren_w, float rec_w, int eh, int ew) -> (Tensor, Tensor)");
+  // ABI 6: the objective with gradients w.r.t. the BRDF maps as well (light_objective(..., brdf_grads=True))
+  m.def("rescale_grads6_(Tensor(a!) g_axis, Tensor(b!) g_lamb, Tensor(c!) g_weight, Tensor(d!) g_albedo, Tensor(e!) g_normal, Tensor(f!) g_rough, Tensor scale, "
+        "Tensor(g!) applied, int parity) -> ()");
+  m.def("attach_grads6(Tensor value, Tensor axis, Tensor lamb, Tensor weight, Tensor albedo, Tensor normal, Tensor rough, Tensor g_axis, Tensor g_lamb, "
+        "Tensor g_weight, Tensor g_albedo, Tensor g_normal, Tensor g_rough, Tensor applied) -> Tensor");
+  m.def("light_objective_brdf_fwdbwd(Tensor albedo, Tensor normal, Tensor rough, Tensor axis, Tensor lamb, Tensor weight, Tensor im, Tensor seg, Tensor env_gt, "
+        "Tensor env_ind, int eh, int ew, float fov, float F0, float[] cam, float ren_w, float rec_w, float offset, bool heads, bool handoff, bool want_albedo, "
+        "bool want_normal, bool want_rough) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("light_objective_brdf(Tensor albedo, Tensor normal, Tensor rough, Tensor axis, Tensor lamb, Tensor weight, Tensor im, Tensor seg, Tensor env_gt, "
+        "Tensor env_ind, int eh, int ew, float fov, float F0, float[] cam, float ren_w, float rec_w, float offset, bool heads, bool handoff) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("light_objective_stage2_brdf(Tensor albedo, Tensor normal, Tensor rough, Tensor axis, Tensor lamb, Tensor weight, Tensor env_gt, Tensor mask, Tensor coef, "
+        "Tensor diffuse, Tensor spec, Tensor im_s, Tensor seg_s, Tensor coef_ds, Tensor sums, Tensor(a!) ws, Tensor lam_t, Tensor w_t, int eh, int ew, float fov, "
+        "float F0, float[] cam, float ren_w, float rec_w, float offset, bool heads, bool want_albedo, bool want_normal, bool want_rough) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   // host-side queries (no tensors, no dispatch key): cached constant tables of a kind (test hook), the objective's workspace size
   m.def("table_cache_count(int kind) -> int", &table_cache_count);
   m.def("cached_tables() -> Tensor[]", &cached_tables);
@@ -1420,6 +1654,11 @@ TORCH_LIBRARY_IMPL(sgrender, CUDA, m) {
   m.impl("light_objective_stage1", &light_objective_stage1_cuda);
   m.impl("light_objective_stage2", &light_objective_stage2_cuda);
   m.impl("light_objective_stage3", &light_objective_stage3_cuda);
+  m.impl("rescale_grads6_", &rescale_grads6_cuda);
+  m.impl("attach_grads6", &attach_grads6_backend);
+  m.impl("light_objective_brdf_fwdbwd", &light_objective_brdf_fwdbwd_cuda);
+  m.impl("light_objective_brdf", &light_objective_backend);
+  m.impl("light_objective_stage2_brdf", &light_objective_stage2_brdf_cuda);
   m.impl("allreduce_sum_", &allreduce_sum_cuda);
 }
 
@@ -1450,6 +1689,11 @@ TORCH_LIBRARY_IMPL(sgrender, Meta, m) {
   m.impl("light_objective_stage1", &light_objective_stage1_meta);
   m.impl("light_objective_stage2", &light_objective_stage2_meta);
   m.impl("light_objective_stage3", &light_objective_stage3_meta);
+  m.impl("rescale_grads6_", &rescale_grads6_meta);
+  m.impl("attach_grads6", &attach_grads6_backend);
+  m.impl("light_objective_brdf_fwdbwd", &light_objective_brdf_fwdbwd_meta);
+  m.impl("light_objective_brdf", &light_objective_backend);
+  m.impl("light_objective_stage2_brdf", &light_objective_stage2_brdf_meta);
   m.impl("allreduce_sum_", &allreduce_sum_meta);
 }
 
@@ -1463,6 +1707,8 @@ TORCH_LIBRARY_IMPL(sgrender, Autograd, m) {
   m.impl("light_heads", &light_heads_autograd);
   m.impl("attach_grads", &attach_grads_autograd);
   m.impl("light_objective", &light_objective_autograd);
+  m.impl("attach_grads6", &attach_grads6_autograd);
+  m.impl("light_objective_brdf", &light_objective_brdf_autograd);
 }
 
 // no CPU path: every operator raises on CPU tensors (a namespace cannot carry a backend fallback, hence one registration each)
@@ -1470,6 +1716,7 @@ TORCH_LIBRARY_IMPL(sgrender, CPU, m) {
   for (const char* name : {"sg_to_env", "sg_to_env_bwd", "render_env", "render_env_bwd_env", "render_bwd_brdf", "fused_render", "fused_render_bwd_sg", "lsregress_coef",
                            "lsregress_diffspec_coef", "render_loss", "render_loss_bwd", "render_loss_finalize", "recon_loss_parts", "recon_loss_bwd", "light_heads", "light_heads_bwd", "sg_shading",
                            "light_albedo_scale", "light_encoder_input", "rescale_grads_", "attach_grads", "light_objective_fwdbwd", "light_objective",
-                           "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "allreduce_sum_"})
+                           "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "allreduce_sum_", "rescale_grads6_", "attach_grads6",
+                           "light_objective_brdf_fwdbwd", "light_objective_brdf", "light_objective_stage2_brdf"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_path>());
 }

@@ -258,14 +258,23 @@ def light_objective_supported(SGNum: int, envRow: int, envCol: int, envHeight: i
 
 def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, lambPred, weightPred, imBatch, segBRDFBatch,
                     envmapsBatch, envmapsIndBatch, renderWeight: float = 1.0, reconWeight: float = 10.0, offset: float = 1.0,
-                    group=None, decoder_outputs: bool = False):
+                    group=None, decoder_outputs: bool = False, brdf_grads: bool = False):
     """The cascade-0 light objective ``renderWeight * renderErr + reconWeight * reconstErr`` of
     wrapperBRDFLight.py:167-207 / trainLight.py:237 in two heavy kernel passes, without ever writing the
     predicted env image or its gradient.
 
     ``renderLayer`` is a :class:`renderingLayer` (its fov / F0 / camera / direction grid are used);
     ``axisPred, lambPred, weightPred`` are the raw decoder outputs (pre-tan), exactly what
-    ``output2env.output2env`` takes.  Differentiable w.r.t. those three only.
+    ``output2env.output2env`` takes.  Differentiable w.r.t. those three only, unless ``brdf_grads=True``.
+
+    ``brdf_grads=True``: also differentiable w.r.t. ``albedoPred``, ``normalPred`` and ``roughPred`` (each that requires grad receives
+    d objective / d map = ``renderWeight`` x d renderErr / d map at the map's own resolution; the reconstruction term does not depend on
+    the maps) -- for training the BRDF networks jointly with, or through, the lighting objective (the reference detaches only
+    ``albedoPred``, wrapperBRDFLight.py:194).  After the objective's backward pass, the render layer's BRDF backward from the SG lobes
+    (one more launch; two from decoder outputs, whose activations it needs) turns the render cotangents that pass already holds into
+    the maps' gradients -- no env image is written; maps at 1x / 2x the env grid are pooled inside the kernels, other sizes through
+    torch's pooling (autograd chains through it).  With no grad-requiring map the call is the default one, launch for launch.  ``imBatch``, ``segBRDFBatch``,
+    ``envmapsBatch`` and ``envmapsIndBatch`` must still not require grad.  The default (``False``) refuses grad-requiring maps.
 
     Configurations without a fused kernel (envWidth other than 16 / 32 or SGNum > 24, see :func:`light_objective_supported`)
     are evaluated by the unfused HIP kernels (forwardSG + render_loss + recon_loss) with the same return values.
@@ -314,6 +323,10 @@ def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, la
         seg = F.adaptive_avg_pool2d(seg, (R, C))
     eh, ew, fov, F0, cam = impl.envHeight, impl.envWidth, impl.fov_deg, float(impl.F0), impl._cam
     handoff = _ops.tan_handoff() and not heads
+    if brdf_grads:
+        return _light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, envmapsBatch, envmapsIndBatch, eh, ew, fov, F0, cam,
+                                     float(renderWeight), float(reconWeight), float(offset), heads, handoff, group,
+                                     (albedoPred, normalPred, roughPred, imBatch, segBRDFBatch, envmapsBatch, envmapsIndBatch))
     # differentiable w.r.t. the SG parameters only -- on BOTH routes (the one-rank operator raised, the sharded route ran its
     # stage operators under no_grad and silently returned no gradient for a BRDF map that still carried one)
     if torch.is_grad_enabled():
@@ -344,4 +357,46 @@ def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, la
     if need:      # every rank holds the gradient of the GLOBAL objective w.r.t. ITS shard (see combine_loss_parts)
         applied = torch.ones(2, device=objective.device, dtype=torch.float32)
         objective = _sg.attach_grads(objective, axisPred, lambPred, weightPred, g_axis, g_lamb, g_weight, applied)
+    return objective, render_err, recon_err, rendered, coef
+
+
+def _light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads,
+                          handoff, group, caller):
+    """:func:`light_objective` with ``brdf_grads=True`` on the fused routes: ``a, n, r`` are the (pre-pooled) maps, ``caller`` the
+    caller's own tensors for the checks."""
+    albedoPred, normalPred, roughPred, imBatch, segBRDFBatch, envmapsBatch, envmapsIndBatch = caller
+    grad = torch.is_grad_enabled()
+    if grad:      # before any launch or collective, on both routes
+        for name, t in (("imBatch", imBatch), ("segBRDFBatch", segBRDFBatch), ("envmapsBatch", envmapsBatch), ("envmapsIndBatch", envmapsIndBatch)):
+            if t.requires_grad:
+                raise RuntimeError(f"sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only; {name} requires grad -- "
+                                   "detach it")
+    live = [grad and t.requires_grad for t in (albedoPred, normalPred, roughPred)]
+    if not _sharded(group):
+        # one operator: with no grad-requiring map it is sgrender::light_objective itself (same launches, same node)
+        return tuple(_sg.light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w,
+                                              offset, heads, handoff))
+    need_sg = grad and (axisPred.requires_grad or lambPred.requires_grad or weightPred.requires_grad)
+    need = need_sg or any(live)
+    with torch.no_grad():
+        diffuse, spec, mask, coef, im_s, seg_s, rendered, coef_ds, sums, ws, lam_t, w_t = _sg.light_objective_stage1(
+            a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, heads, handoff and need)
+        _allreduce_sum_(sums, group)      # [num_r, den_r, 0, den_e]: one all-reduce before the backward pass
+        if any(live):
+            render_err, g_axis, g_lamb, g_weight, g_alb, g_nrm, g_rgh, parts_b = _sg.light_objective_stage2_brdf(
+                a, n, r, axisPred, lambPred, weightPred, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
+                eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, live[0], live[1], live[2])
+        else:
+            render_err, g_axis, g_lamb, g_weight, parts_b = _sg.light_objective_stage2(
+                a, n, r, axisPred, lambPred, weightPred, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
+                eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, need)
+        num_e = parts_b[0:1]
+        _allreduce_sum_(num_e, group)     # the second and last collective: the reconstruction numerator
+        objective, recon_err = _sg.light_objective_stage3(render_err, num_e, sums, ren_w, rec_w, eh, ew)
+    if need:      # every rank holds the gradient of the GLOBAL objective w.r.t. ITS shard (see combine_loss_parts)
+        applied = torch.ones(2, device=objective.device, dtype=torch.float32)
+        if any(live):
+            objective = _sg.attach_grads6(objective, axisPred, lambPred, weightPred, a, n, r, g_axis, g_lamb, g_weight, g_alb, g_nrm, g_rgh, applied)
+        else:
+            objective = _sg.attach_grads(objective, axisPred, lambPred, weightPred, g_axis, g_lamb, g_weight, applied)
     return objective, render_err, recon_err, rendered, coef
