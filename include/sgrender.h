@@ -406,6 +406,42 @@ int sgr_light_input_fwd(const float* im, const float* albedo, const float* norma
                         float* out, float* albedo_norm, float* depth_norm, float* workspace, int bn, int h, int w, int H, int W,
                         void* stream);
 
+/* ---- the bilateral solver layer (BilateralLayer.py:20-124, BilateralGrid.py:43-207) ------------------------------
+ * Batched over B images of H x W pixels (N = H*W) and C = 1..3 target channels, fp64 inside, nothing read back to the host.
+ * nvertices <= N, so image b owns the slots [b*N, (b+1)*N) of every per-vertex array; nvert[b] stays on the device.
+ * The grid ("grid tensors" below; vertex indices are per image):
+ *   pix2vert int32 [B,N]      pixel -> vertex (vertices = distinct 5-D hashes in ascending order, np.unique's numbering)
+ *   perm     int32 [B,N]      pixels sorted by vertex, ascending pixel index inside a vertex
+ *   seg      int32 [B,N]      vertex -> first position of its pixels in perm
+ *   nbr      int32 [B,N,10]   vertex -> neighbour along -+x, -+y, -+luma, -+U, -+V; -1 = absent
+ *   nvert    int32 [B]
+ *   m, n     fp64  [B,N]      the bistochastisation's diagonals (BilateralGrid.py:106-118)
+ * Contract: BilateralGrid.solve / solveForGrad with scipy's cg(rtol = cg_tol, atol = 0, maxiter = cg_maxiter). */
+
+/* Bytes of workspace for the calls below (the largest of them); negative = SGR_ERR_*.  Pure host function. */
+long long sgr_bs_workspace_bytes(int B, int H, int W, int C);
+
+/* keys [B*N] int64 = image index * 2^44 + 5-D hash + 2^43 of every pixel of image [B,3,H,W] (fp32, the guide in [0,1]; coordinates
+ * in fp64 as BilateralGrid.py:43-60).  The caller sorts them with ANY STABLE sort, keeping the sorted positions' original
+ * indices (int64, 0..B*N-1), and hands both to sgr_bs_grid_build.  Colour bandwidths below 0.25 are unsupported. */
+int sgr_bs_grid_keys(const float* image, long long* keys, int B, int H, int W, double sigma_luma, double sigma_chroma,
+                     double sigma_spatial, void* stream);
+
+/* The grid tensors from the sorted keys: vertex numbering, neighbour table, ten bistochastisation sweeps. */
+int sgr_bs_grid_build(const long long* sorted_keys, const long long* sorted_index, int* pix2vert, int* perm, int* seg, int* nbr,
+                      int* nvert, double* m, double* n, void* workspace, int B, int H, int W, void* stream);
+
+/* BilateralGrid.solve: out [B,C,H,W] = slice(yhat), yhat [B,N,C] fp64 (kept for the backward).  pred [B,C,H,W], conf [B,H,W]. */
+int sgr_bs_solve_fwd(const int* pix2vert, const int* perm, const int* seg, const int* nbr, const int* nvert, const double* m,
+                     const double* n, const float* pred, const float* conf, float* out, double* yhat, void* workspace, int B, int C,
+                     int H, int W, double lam, double A_diag_min, double cg_tol, int cg_maxiter, void* stream);
+
+/* BilateralGrid.solveForGrad: g_pred [B,C,H,W] = slice(yb) conf, g_conf [B,H,W] = sum_c slice(-yb yhat) + slice(yb) pred. */
+int sgr_bs_solve_bwd(const int* pix2vert, const int* perm, const int* seg, const int* nbr, const int* nvert, const double* m,
+                     const double* n, const float* g_out, const float* pred, const float* conf, const double* yhat, float* g_pred,
+                     float* g_conf, void* workspace, int B, int C, int H, int W, double lam, double A_diag_min, double cg_tol,
+                     int cg_maxiter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

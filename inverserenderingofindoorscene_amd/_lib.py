@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGR_LIB", os.path.join(_HERE, "libsgrender.so"))
@@ -32,6 +32,7 @@ class SgrenderError(RuntimeError):
 _P = c_void_p   # device / host pointers travel as plain addresses
 _I = c_int
 _F = c_float
+_D = c_double
 
 # symbol -> argument types; must mirror include/sgrender.h exactly (tests/test_abi.py checks
 # that every function declared in the header is exported and listed here).
@@ -82,6 +83,11 @@ SIGNATURES = {
     "sgr_glue_workspace_floats": ([_I], c_int),
     "sgr_light_albedo_scale": ([_P] * 7 + [ctypes.c_longlong, ctypes.c_longlong, _P], c_int),
     "sgr_light_input_fwd": ([_P] * 9 + [_I] * 5 + [_P], c_int),
+    "sgr_bs_workspace_bytes": ([_I] * 4, c_longlong),
+    "sgr_bs_grid_keys": ([_P, _P] + [_I] * 3 + [_D] * 3 + [_P], c_int),
+    "sgr_bs_grid_build": ([_P] * 10 + [_I] * 3 + [_P], c_int),
+    "sgr_bs_solve_fwd": ([_P] * 12 + [_I] * 4 + [_D] * 3 + [_I, _P], c_int),
+    "sgr_bs_solve_bwd": ([_P] * 14 + [_I] * 4 + [_D] * 3 + [_I, _P], c_int),
 }
 
 _lib = None
