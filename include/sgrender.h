@@ -442,6 +442,57 @@ int sgr_bs_solve_bwd(const int* pix2vert, const int* perm, const int* seg, const
                      float* g_conf, void* workspace, int B, int C, int H, int W, double lam, double A_diag_min, double cg_tol,
                      int cg_maxiter, void* stream);
 
+/* ---- the BRDF-stage training objectives (wrapperBRDF.py:109-130 = trainBRDF.py:248-286, wrapperNYU.py:97-111, wrapperIIW.py:88-109) ----
+ * Predictions and ground truth: albedo / normal [bn,3,H,W], rough / depth [bn,1,H,W]; masks seg_brdf, seg_all, seg_depth [bn,1,H,W] with
+ * values in [0,1] (not assumed binary).  A NULL prediction (with its ground truth NULL too) leaves that term out: it is neither read nor
+ * written and its error is 0.  seg_brdf masks albedo and roughness, seg_all masks the normal, seg_depth (NULL = seg_all) the depth.
+ * `albedo_pred` / `depth_pred` are the wrappers' tensors of those names (after 0.5 (decoder + 1)).  Contract: DESIGN.md section 8b.
+ *   coef   [bn,2]  the (albedo, depth) LSregress coefficients (models.py:13-14), 0 for an absent term
+ *   parts  [8]     (numAlbedo, numNormal, numRough, numDepth, numAngle, nObj, nAll, nDep): this rank's batch totals, to be summed over
+ *                  ranks when the batch is sharded
+ *   values [6]     (total, albedoErr, normalErr, roughErr, depthErr, angleMean in degrees) with the denominators through max(., 1e-5)
+ *                  and total = w_albedo albedoErr + w_normal normalErr + w_rough roughErr + w_depth depthErr */
+
+/* Floats of workspace for sgr_brdf_objective_fwd.  Pure host function. */
+int sgr_brdf_objective_workspace_floats(int bn);
+
+/* Three launches: coef, parts and -- unless `values` is NULL (sharded batches: all-reduce parts, then sgr_brdf_objective_finalize) -- values. */
+int sgr_brdf_objective_fwd(const float* albedo_pred, const float* albedo, const float* normal_pred, const float* normal,
+                           const float* rough_pred, const float* rough, const float* depth_pred, const float* depth,
+                           const float* seg_brdf, const float* seg_all, const float* seg_depth, float* coef, float* parts, float* values,
+                           float* workspace, int bn, int H, int W, float w_albedo, float w_normal, float w_rough, float w_depth,
+                           float depth_offset, void* stream);
+
+/* values [6] from the (rank-summed) parts [8]. */
+int sgr_brdf_objective_finalize(const float* parts, float* values, float w_albedo, float w_normal, float w_rough, float w_depth,
+                                void* stream);
+
+/* One launch: the gradients of  g_total total + g_albedo_err albedoErr + ... + g_depth_err depthErr  with respect to the predictions.
+ * The five upstream gradients are device scalars, each nullable (= 0).  g_*_pred: nullable = not wanted (that term's planes are not
+ * read).  The coefficients are constants (models.py:13 detaches them); the albedo clamp passes gradient on 0 <= albedo_pred coef <= 1.
+ * `parts` holds the GLOBAL denominators (after the all-reduce when sharded). */
+int sgr_brdf_objective_bwd(const float* g_total, const float* g_albedo_err, const float* g_normal_err, const float* g_rough_err,
+                           const float* g_depth_err, const float* albedo_pred, const float* albedo, const float* normal_pred,
+                           const float* normal, const float* rough_pred, const float* rough, const float* depth_pred, const float* depth,
+                           const float* seg_brdf, const float* seg_all, const float* seg_depth, const float* coef, const float* parts,
+                           float* g_albedo_pred, float* g_normal_pred, float* g_rough_pred, float* g_depth_pred, int bn, int H, int W,
+                           float w_albedo, float w_normal, float w_rough, float w_depth, float depth_offset, void* stream);
+
+/* The IIW ranking objective of a whole batch (models.py:526-563 per image, wrapperIIW.py:105-109 over the batch).
+ *   albedo_pred [B,3,H,W];  *_point int32 [B,N,4] = (r1,c1,r2,c2);  *_weight [B,N];  *_num int32 [B] (clamped to 0..N; entries at or
+ *   beyond it are ignored whatever they hold; a judgement with a row or column outside the image counts as weight 0 and is never
+ *   dereferenced; an image with num == 0 contributes 0).  out2 = (eqLoss, darkerLoss).  2 (n_eq + n_darker) <= 4096. */
+int sgr_ranking_loss_workspace_floats(int B);
+int sgr_ranking_loss_fwd(const float* albedo_pred, const int* eq_point, const float* eq_weight, const int* eq_num,
+                         const int* darker_point, const float* darker_weight, const int* darker_num, float* out2, float* workspace,
+                         int B, int H, int W, int n_eq, int n_darker, float tau, void* stream);
+/* g_albedo_pred [B,3,H,W] (dense, zero off the judged pixels) for the device scalars g_eq, g_darker (nullable = 0).  Judgements that
+ * share a pixel are added in a fixed order (sorted endpoint records): bit-reproducible, no float atomics. */
+int sgr_ranking_loss_bwd(const float* g_eq, const float* g_darker, const float* albedo_pred, const int* eq_point,
+                         const float* eq_weight, const int* eq_num, const int* darker_point, const float* darker_weight,
+                         const int* darker_num, float* g_albedo_pred, int B, int H, int W, int n_eq, int n_darker, float tau,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

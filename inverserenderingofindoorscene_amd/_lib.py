@@ -88,6 +88,13 @@ SIGNATURES = {
     "sgr_bs_grid_build": ([_P] * 10 + [_I] * 3 + [_P], c_int),
     "sgr_bs_solve_fwd": ([_P] * 12 + [_I] * 4 + [_D] * 3 + [_I, _P], c_int),
     "sgr_bs_solve_bwd": ([_P] * 14 + [_I] * 4 + [_D] * 3 + [_I, _P], c_int),
+    "sgr_brdf_objective_workspace_floats": ([_I], c_int),
+    "sgr_brdf_objective_fwd": ([_P] * 15 + [_I] * 3 + [_F] * 5 + [_P], c_int),
+    "sgr_brdf_objective_finalize": ([_P, _P] + [_F] * 4 + [_P], c_int),
+    "sgr_brdf_objective_bwd": ([_P] * 22 + [_I] * 3 + [_F] * 5 + [_P], c_int),
+    "sgr_ranking_loss_workspace_floats": ([_I], c_int),
+    "sgr_ranking_loss_fwd": ([_P] * 9 + [_I] * 5 + [_F, _P], c_int),
+    "sgr_ranking_loss_bwd": ([_P] * 10 + [_I] * 5 + [_F, _P], c_int),
 }
 
 _lib = None

@@ -14,7 +14,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "libsgrender_torch.so")
-SOURCES = [os.path.join(HERE, "sgr_torch.cpp"), os.path.join(HERE, "sgr_torch_bilateral.cpp")]
+SOURCES = [os.path.join(HERE, "sgr_torch.cpp"), os.path.join(HERE, "sgr_torch_bilateral.cpp"), os.path.join(HERE, "sgr_torch_brdf.cpp")]
 DEPS = SOURCES + [os.path.join(HERE, "..", "..", "include", "sgrender.h"), os.path.abspath(__file__)]
 
 
