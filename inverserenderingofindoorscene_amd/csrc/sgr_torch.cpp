@@ -13,9 +13,9 @@
 //                                                                rounds 2-3 had a Python custom_op AND a Python autograd.Function)
 //   * CPU:       a boxed fallback that raises -- there is no CPU path and no fallback to one.
 //
-// The C ABI stays the drop-in boundary: it is resolved with dlopen at first use ($SGR_LIB, else the libsgrender.so next to this
-// file's .so), so development builds of the kernel library can be A/B-ed under the same host layer, and a missing library is a
-// loud error, not a silent fallback.
+// The C ABI stays the drop-in boundary: sgr_torch_common.hpp resolves it once, at first use, for this file and its siblings of the same
+// extension (sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp) and holds the helpers the three share.  The light objective is ONE path:
+// objective_fwdbwd / objective_stage2 / PrecomputedGradsFn serve the SG-only operators and their _brdf twins alike (MapWants).
 //
 // Reference call each public operator stands for (file:line relative to the reference checkout):
 //   sg_to_env          output2env.output2env / fromSGtoIm            models.py:371-404
@@ -27,106 +27,27 @@
 //   light_objective    renW * renderErr + recW * reconstErr, fused   wrapperBRDFLight.py:167-207, trainLight.py:237
 //   lsregress_*_coef   LSregress / LSregressDiffSpec coefficients    models.py:7-21, 23-84
 //   sg_shading, light_albedo_scale, light_encoder_input             utils.py:156-195, testReal.py:421-432, wrapperBRDFLight.py:138-156
-#include <dlfcn.h>
 #include <link.h>
 
-#include <cstdlib>
+#include <array>
 #include <cstring>
 #include <deque>
 #include <map>
 #include <mutex>
-#include <string>
-#include <tuple>
 #include <vector>
 
-#include <ATen/ATen.h>
-#include <ATen/core/dispatch/Dispatcher.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/csrc/autograd/custom_function.h>
-#include <torch/library.h>
+#include "sgr_torch_common.hpp"
 
 #include <rccl/rccl.h>      // declarations only: the functions are resolved from the RCCL PyTorch itself has loaded (rccl() below)
 
-#include "../../include/sgrender.h"
-
 namespace {
 
-using at::Tensor;
-using OptTensor = std::optional<Tensor>;
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-using T2 = std::tuple<Tensor, Tensor>;
-using T3 = std::tuple<Tensor, Tensor, Tensor>;
-using T4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
-using T5 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>;
+using namespace sgr_host;
 using Cam = at::ArrayRef<double>;
 
 // ------------------------------------------------------------------------------------------------------------------
-// the C ABI, resolved at first use
+// argument checks, constant tables
 // ------------------------------------------------------------------------------------------------------------------
-#define SGR_API_LIST(X)                                                                                                          \
-  X(sgr_abi_version) X(sgr_last_error) X(sgr_dirs_floats) X(sgr_fill_direction_table) X(sgr_fill_view_vectors)                   \
-  X(sgr_sg_to_env_fwd) X(sgr_render_env_fwd) X(sgr_fused_fwd_tan) X(sgr_sg_to_env_bwd) X(sgr_fused_bwd_sg)                        \
-  X(sgr_render_env_bwd_env) X(sgr_render_bwd_brdf) X(sgr_loss_workspace_floats) X(sgr_render_loss_fwd)                           \
-  X(sgr_render_loss_fwd_total) X(sgr_render_loss_fwd_total_grads) X(sgr_loss_finalize) X(sgr_objective_finalize) X(sgr_render_loss_bwd_scaled)                      \
-  X(sgr_lsregress_coef) X(sgr_lsregress_diffspec_coef) X(sgr_sg_shading) X(sgr_recon_workspace_floats) X(sgr_recon_loss_fwd)     \
-  X(sgr_recon_loss_bwd) X(sgr_fused_recon_supported) X(sgr_heads_prologue_supported) X(sgr_fused_recon_workspace_floats)         \
-  X(sgr_fused_fwd_recon_seg) X(sgr_light_objective_fwd) X(sgr_light_heads_fwd) X(sgr_light_heads_bwd) X(sgr_rescale_inplace_flip) X(sgr_fused_bwd_recon)    \
-  X(sgr_fused_bwd_recon_total) X(sgr_glue_workspace_floats) X(sgr_light_albedo_scale) X(sgr_light_input_fwd)                  \
-  X(sgr_fused_bwd_recon_brdf) X(sgr_fused_bwd_recon_total_brdf)
-
-struct Api {
-#define SGR_DECL(name) decltype(&::name) name = nullptr;
-  SGR_API_LIST(SGR_DECL)
-#undef SGR_DECL
-  std::string path;
-};
-
-void anchor() {}
-
-const Api& api() {
-  static const Api a = [] {
-    Api r;
-    const char* env = std::getenv("SGR_LIB");
-    if (env && env[0]) {
-      r.path = env;
-    } else {
-      Dl_info info{};
-      TORCH_CHECK(dladdr(reinterpret_cast<void*>(&anchor), &info) && info.dli_fname, "sgrender: cannot locate the torch extension on disk");
-      std::string self = info.dli_fname;
-      const auto slash = self.find_last_of('/');
-      r.path = (slash == std::string::npos ? std::string(".") : self.substr(0, slash)) + "/libsgrender.so";
-    }
-    void* h = dlopen(r.path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    TORCH_CHECK(h, "sgrender: cannot load ", r.path, " (", dlerror(), "): the HIP library has not been built -- run "
-                "__graft_entry__.build() or `make -C inverserenderingofindoorscene_amd/csrc`.  This package has no CPU / PyTorch fallback.");
-#define SGR_LOAD(name)                                                                     \
-  r.name = reinterpret_cast<decltype(r.name)>(dlsym(h, #name));                            \
-  TORCH_CHECK(r.name, "sgrender: ", r.path, " does not export " #name "; stale build?");
-    SGR_API_LIST(SGR_LOAD)
-#undef SGR_LOAD
-    TORCH_CHECK(r.sgr_abi_version() == SGR_ABI_VERSION, "sgrender: ", r.path, " has ABI version ", r.sgr_abi_version(), ", this extension needs ",
-                SGR_ABI_VERSION);
-    return r;
-  }();
-  return a;
-}
-
-void ok(int rc, const char* what) {
-  if (rc != 0) {
-    const char* msg = api().sgr_last_error();
-    TORCH_CHECK(false, "sgrender: ", what, " failed (code ", rc, "): ", msg ? msg : "");
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// argument checks, pointers, stream, constant tables
-// ------------------------------------------------------------------------------------------------------------------
-constexpr const char* kNoCpu =
-    "sgrender: this layer runs only on HIP device tensors (MI355X); there is no CPU path. Move the inputs to the GPU (the reference's "
-    "isCuda=True mode).";
-
 void require_one(const Tensor& t, c10::Device& dev, bool& have) {
   TORCH_CHECK(t.is_cuda(), kNoCpu);
   TORCH_CHECK(t.scalar_type() == at::kFloat, "sgrender: fp32 tensors required, got ", t.scalar_type());
@@ -147,11 +68,6 @@ c10::Device require_hip(std::initializer_list<const Tensor*> ts) {
 }
 const Tensor* opt(const OptTensor& t) { return t.has_value() && t->defined() ? &*t : nullptr; }
 
-const float* rp(const Tensor& t) { return t.defined() && t.numel() ? t.const_data_ptr<float>() : nullptr; }
-float* wp(const Tensor& t) { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; }
-const float* rp(const Tensor* t) { return t ? rp(*t) : nullptr; }
-
-void* stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStream(dev.index()).stream(); }
 
 struct SgDims { int64_t bn, K, R, C; };
 SgDims check_sg(const Tensor& axis, const Tensor& lamb, const Tensor& weight) {
@@ -248,14 +164,8 @@ Tensor view_table(const c10::Device& dev, int64_t R, int64_t C, double fov, Cam 
 }
 
 Tensor none_like(const Tensor& t) { return at::empty({0}, t.options()); }      // operators return tensors only: "not asked for" is an empty tensor
-Tensor defined_or_none(const Tensor& t) { return t; }
 bool present(const Tensor& t) { return t.defined() && t.numel() > 0; }
 std::vector<double> vec(Cam cam) { return std::vector<double>(cam.begin(), cam.end()); }
-
-template <typename Sig>
-auto find_op(const char* name) {
-  return c10::Dispatcher::singleton().findSchemaOrThrow(name, "").typed<Sig>();
-}
 
 // ==================================================================================================================
 // SG -> env image
@@ -618,7 +528,6 @@ Tensor lsregress_diffspec_coef_meta(const Tensor& diff, const Tensor&, const Ten
 //   total = true  (one rank):  loss = renderErr, scale = d loss / d numerator; three launches (the third pass forms the value)
 //   total = false (sharded):   loss / scale empty; parts = (numerator, raw denominator) of this shard, all-reduced by the caller
 // differentiable outputs: loss (total) or parts (sharded; only its numerator carries a gradient)
-using T7 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 T7 render_loss_cuda(const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C, bool total) {
   const auto dev = require_hip({&diffuse, &spec, &im, &seg});
   const c10::DeviceGuard guard(dev);
@@ -941,25 +850,60 @@ T3 light_encoder_input_meta(const Tensor& im, const Tensor& albedo, const Tensor
 // ==================================================================================================================
 // the whole trainLight objective, env image never materialised              wrapperBRDFLight.py:167-207, trainLight.py:237
 // ==================================================================================================================
+// Which BRDF maps want a gradient (light_objective(..., brdf_grads=True)): the ONE thing that tells an SG-only operator from its _brdf
+// twin.  Both run the same routine and the same launches; with a map wanted, the render layer's BRDF backward from the SG lobes follows,
+// driven by the render cotangents the objective's pass already holds (inside sgr_fused_bwd_recon_total_brdf / sgr_fused_bwd_recon_brdf,
+// which with NULL map outputs are exactly the plain entry points).  Inside the shared routines an output nobody asked for is an undefined
+// tensor; operators return tensors only, so the adapters turn it into an empty one.
+struct MapWants {
+  bool albedo = false, normal = false, rough = false;
+  bool any() const { return albedo || normal || rough; }
+};
+Tensor or_none(const Tensor& t, const Tensor& like) { return t.defined() ? t : none_like(like); }
+template <size_t... I, typename Tuple>
+auto pick(const Tuple& t, const Tensor& like) { return std::make_tuple(or_none(std::get<I>(t), like)...); }      // an operator's outputs out of a shared routine's
+
 // Gradients that exist before backward() is called (the objective's heavy backward pass also produces the loss value, so it
 // runs in forward): a node that hands them out times the incoming cotangent.  The scaling happens in place on the device
 // (sgr_rescale_inplace_flip: a no-op kernel when the cotangent equals what the gradients are scaled by already -- 1 for a
 // plain objective.backward()); `applied` holds two slots, the factor currently applied in applied[parity].
-void rescale_grads_cuda(Tensor& g_axis, Tensor& g_lamb, Tensor& g_weight, const Tensor& scale, Tensor& applied, int64_t parity) {
-  const auto dev = require_hip({&g_axis, &g_lamb, &g_weight, &scale, &applied});
+// One launch scales at most three tensors; launches with the same parity each read applied[parity] and write the new factor to the other
+// slot.  So: the SG trio (gs[0..2]) in one launch, then whichever map gradients (gs[3..5], may be NULL) are present in a second.
+void rescale_grads(std::array<Tensor*, 6> gs, const Tensor& scale, Tensor& applied, int64_t parity, const char* what) {
+  const auto dev = require_hip({gs[0], gs[1], gs[2], &scale, &applied});
   const c10::DeviceGuard guard(dev);
-  TORCH_CHECK(g_axis.is_contiguous() && g_lamb.is_contiguous() && g_weight.is_contiguous() && applied.numel() == 2 && scale.numel() == 1, "sgrender: rescale_grads_ arguments");
-  float* xs[3] = {g_axis.data_ptr<float>(), g_lamb.data_ptr<float>(), g_weight.data_ptr<float>()};
-  const long long ns[3] = {(long long)g_axis.numel(), (long long)g_lamb.numel(), (long long)g_weight.numel()};
+  TORCH_CHECK(applied.numel() == 2 && scale.numel() == 1, what);
   const Tensor sc = scale.contiguous();
-  ok(api().sgr_rescale_inplace_flip(xs, ns, 3, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
+  for (int first : {0, 3}) {
+    float* xs[3];
+    long long ns[3];
+    int count = 0;
+    for (int k = first; k < first + 3; ++k) {
+      if (first && !(gs[k] && present(*gs[k]))) continue;
+      TORCH_CHECK(gs[k]->is_contiguous() && gs[k]->device() == dev, what);
+      xs[count] = gs[k]->data_ptr<float>();
+      ns[count++] = (long long)gs[k]->numel();
+    }
+    if (count) ok(api().sgr_rescale_inplace_flip(xs, ns, count, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
+  }
+}
+void rescale_grads_cuda(Tensor& g_axis, Tensor& g_lamb, Tensor& g_weight, const Tensor& scale, Tensor& applied, int64_t parity) {
+  rescale_grads({&g_axis, &g_lamb, &g_weight, nullptr, nullptr, nullptr}, scale, applied, parity, "sgrender: rescale_grads_ arguments");
 }
 void rescale_grads_meta(Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t) {}
+void rescale_grads6_cuda(Tensor& g_axis, Tensor& g_lamb, Tensor& g_weight, Tensor& g_albedo, Tensor& g_normal, Tensor& g_rough, const Tensor& scale,
+                         Tensor& applied, int64_t parity) {
+  rescale_grads({&g_axis, &g_lamb, &g_weight, &g_albedo, &g_normal, &g_rough}, scale, applied, parity, "sgrender: rescale_grads6_ arguments");
+}
+void rescale_grads6_meta(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t) {}
 
 struct PrecomputedGradsFn : public torch::autograd::Function<PrecomputedGradsFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& g_axis,
-                        const Tensor& g_lamb, const Tensor& g_weight, const Tensor& applied) {
-    ctx->save_for_backward({g_axis, g_lamb, g_weight, applied});
+  // inputs: value, axis, lamb, weight, albedo, normal, rough, then their six gradients and `applied`.  A map's gradient is absent when
+  // nobody asked for it: nullopt on the SG-only route (its map too: not an input of the node), an empty tensor on the others.
+  static Tensor forward(AutogradContext* ctx, const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const OptTensor& albedo,
+                        const OptTensor& normal, const OptTensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight,
+                        const OptTensor& g_albedo, const OptTensor& g_normal, const OptTensor& g_rough, const Tensor& applied) {
+    ctx->save_for_backward({g_axis, g_lamb, g_weight, g_albedo.value_or(Tensor()), g_normal.value_or(Tensor()), g_rough.value_or(Tensor()), applied});
     ctx->saved_data["parity"] = (int64_t)0;
     ctx->saved_data["handed_out"] = false;
     ctx->set_materialize_grads(false);
@@ -967,10 +911,11 @@ struct PrecomputedGradsFn : public torch::autograd::Function<PrecomputedGradsFn>
     return value.alias();
   }
   static variable_list backward(AutogradContext* ctx, variable_list g) {
-    variable_list out(8);
+    variable_list out(14);
     if (!g[0].defined()) return out;
     const auto saved = ctx->get_saved_variables();
-    Tensor g_axis = saved[0], g_lamb = saved[1], g_weight = saved[2], applied = saved[3];
+    Tensor gs[6] = {saved[0], saved[1], saved[2], saved[3], saved[4], saved[5]};
+    Tensor applied = saved[6];
     const int64_t parity = ctx->saved_data["parity"].toInt();
     if (ctx->saved_data["handed_out"].toBool()) {
       // a second backward through this node (retain_graph): the buffers may be somebody's .grad by now -- leave them alone.  If the
@@ -979,28 +924,42 @@ struct PrecomputedGradsFn : public torch::autograd::Function<PrecomputedGradsFn>
       TORCH_CHECK(applied[parity].item<float>() != 0.0f, "sgrender: light_objective was first back-propagated with a zero cotangent; its stored "
                   "gradients are gone -- re-evaluate the objective instead of reusing the graph");
       const Tensor f = g[0].detach() / applied[parity];
-      if (ctx->needs_input_grad(1)) out[1] = g_axis * f;
-      if (ctx->needs_input_grad(2)) out[2] = g_lamb * f;
-      if (ctx->needs_input_grad(3)) out[3] = g_weight * f;
+      for (int i = 0; i < 6; ++i)
+        if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i] * f;
       return out;
     }
     ctx->saved_data["handed_out"] = true;
-    static auto op = find_op<void(Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t)>("sgrender::rescale_grads_");
-    op.call(g_axis, g_lamb, g_weight, g[0].detach().to(at::kFloat).reshape({1}), applied, parity);
+    const Tensor scale = g[0].detach().to(at::kFloat).reshape({1});
+    if (present(gs[3]) || present(gs[4]) || present(gs[5])) {
+      static auto op = find_op<void(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t)>("sgrender::rescale_grads6_");
+      op.call(gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], scale, applied, parity);
+    } else {
+      static auto op = find_op<void(Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t)>("sgrender::rescale_grads_");
+      op.call(gs[0], gs[1], gs[2], scale, applied, parity);
+    }
     ctx->saved_data["parity"] = (int64_t)(1 - parity);
-    if (ctx->needs_input_grad(1)) out[1] = g_axis;
-    if (ctx->needs_input_grad(2)) out[2] = g_lamb;
-    if (ctx->needs_input_grad(3)) out[3] = g_weight;
+    for (int i = 0; i < 6; ++i)
+      if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i];
     return out;
   }
 };
-// Python-callable face of the node (the sharded objective assembles its value from stage operators and collectives)
+// Python-callable faces of the node (the sharded objective assembles its value from stage operators and collectives)
 Tensor attach_grads_backend(const Tensor& value, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
   return value.clone();
 }
 Tensor attach_grads_autograd(const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& g_axis, const Tensor& g_lamb,
                              const Tensor& g_weight, const Tensor& applied) {
-  return PrecomputedGradsFn::apply(value, axis, lamb, weight, g_axis, g_lamb, g_weight, applied);
+  const OptTensor no;
+  return PrecomputedGradsFn::apply(value, axis, lamb, weight, no, no, no, g_axis, g_lamb, g_weight, no, no, no, applied);
+}
+Tensor attach_grads6_backend(const Tensor& value, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                             const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
+  return value.clone();
+}
+Tensor attach_grads6_autograd(const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& albedo, const Tensor& normal,
+                              const Tensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight, const Tensor& g_albedo, const Tensor& g_normal,
+                              const Tensor& g_rough, const Tensor& applied) {
+  return PrecomputedGradsFn::apply(value, axis, lamb, weight, albedo, normal, rough, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied);
 }
 
 struct ObjDims { int64_t bn, K, R, C, h, w, imH, imW; };
@@ -1016,75 +975,124 @@ ObjDims check_objective(const Tensor& albedo, const Tensor& normal, const Tensor
   return {d.bn, d.K, d.R, d.C, b.h, b.w, im.size(2), im.size(3)};
 }
 
-// light_objective_fwdbwd(...) -> (objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, applied)
-// One rank.  need_grad: forward statistics pass -> render loss (3 launches, value included) -> render-loss backward -> the
-// objective's backward pass (SG gradients + reconstruction numerator + the scalar tail in its fold): ten launches, eight of them
-// small.  !need_grad (round 4, forward-only callers): the last pass runs without its gradient half (sgr_fused_bwd_recon_total
-// with NULL gradient outputs) and the render-loss backward is skipped; the gradient outputs are empty.
-using T9 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
-T9 light_objective_fwdbwd_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                               const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam,
-                               double ren_w, double rec_w, double offset, bool heads, bool handoff, bool need_grad) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind});
-  const c10::DeviceGuard guard(dev);
-  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const Tensor i = im.contiguous(), sg = seg.contiguous(), gt = env_gt.contiguous(), ind = env_ind.contiguous().reshape({-1});
-  const auto d = check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew);
-  const auto o = a.options();
+// the ten tensors and the layer constants every one-rank objective operator takes, and the objective's own options
+#define OBJ_INPUTS                                                                                                                                       \
+  const Tensor &albedo, const Tensor &normal, const Tensor &rough, const Tensor &axis, const Tensor &lamb, const Tensor &weight, const Tensor &im,        \
+      const Tensor &seg, const Tensor &env_gt, const Tensor &env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam
+#define OBJ_INPUTS_PASS albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam
+#define OBJ_ARGS OBJ_INPUTS, double ren_w, double rec_w, double offset, bool heads, bool handoff
+#define OBJ_PASS OBJ_INPUTS_PASS, ren_w, rec_w, offset, heads, handoff
+
+// What the one-rank objective and stage 1 of the sharded one do before their first launch: contiguous inputs, the argument checks, the
+// temporaries both fill, the two constant tables.  (A constructor, so that the device guard lives as long as the caller's frame.)
+struct ObjectivePrologue {
+  c10::Device dev;
+  c10::DeviceGuard guard;
+  Tensor a, n, r, ax, la, we, i, sg, gt, ind;
+  ObjDims d;
+  at::TensorOptions o;
+  int bn, K, R, C;
+  Tensor diffuse, spec, im_s, seg_s, rendered, mask, coef, coef_ds, ws, ws_r, dirs, view;
+  void* st;
+  explicit ObjectivePrologue(OBJ_INPUTS)
+      : dev(require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind})), guard(dev), a(albedo.contiguous()),
+        n(normal.contiguous()), r(rough.contiguous()), ax(axis.contiguous()), la(lamb.contiguous()), we(weight.contiguous()), i(im.contiguous()),
+        sg(seg.contiguous()), gt(env_gt.contiguous()), ind(env_ind.contiguous().reshape({-1})), d(check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew)),
+        o(a.options()), bn((int)d.bn), K((int)d.K), R((int)d.R), C((int)d.C) {
+    auto img = [&] { return at::empty({d.bn, 3, d.R, d.C}, o); };
+    diffuse = img(); spec = img(); im_s = img(); rendered = img();
+    seg_s = at::empty({d.bn, 1, d.R, d.C}, o); mask = at::empty({d.bn, d.R * d.C}, o); coef = at::empty({d.bn}, o); coef_ds = at::empty({d.bn, 2}, o);
+    ws = at::empty({api().sgr_fused_recon_workspace_floats(bn, R, C)}, o); ws_r = loss_workspace(d.bn, a);
+    dirs = dirs_table(dev, eh, ew); view = view_table(dev, d.R, d.C, fov, cam);
+    st = stream_of(dev);
+  }
+};
+
+// Decoder outputs (heads) with a map gradient wanted: the BRDF backward needs the activated SG parameters -- sgr_light_heads_fwd into
+// temporaries, then the layer's BRDF backward from them (premap 1) driven by the objective's render cotangents; the SG pass itself keeps the
+// heads as its prologue.
+void heads_brdf_pass(const Tensor& ax, const Tensor& la, const Tensor& we, const Tensor& a, const Tensor& n, const Tensor& r, const Tensor& g_d,
+                     const Tensor& g_s, const Tensor& dirs, const Tensor& view, Tensor& g_alb, Tensor& g_nrm, Tensor& g_rgh, int64_t bn, int64_t K,
+                     int64_t R, int64_t C, int64_t eh, int64_t ew, int64_t h, int64_t w, double F0, void* st) {
   const Api& A = api();
-  void* st = stream_of(dev);
-  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
-  Tensor diffuse = at::empty({d.bn, 3, d.R, d.C}, o), spec = at::empty({d.bn, 3, d.R, d.C}, o), im_s = at::empty({d.bn, 3, d.R, d.C}, o);
-  Tensor seg_s = at::empty({d.bn, 1, d.R, d.C}, o), rendered = at::empty({d.bn, 3, d.R, d.C}, o), mask = at::empty({d.bn, d.R * d.C}, o), coef = at::empty({d.bn}, o);
-  Tensor coef_ds = at::empty({d.bn, 2}, o), parts_r = at::empty({2}, o), parts_b = at::empty({2}, o), scale_r = at::empty({1}, o);
-  Tensor ws = at::empty({A.sgr_fused_recon_workspace_floats(bn, R, C)}, o), ws_r = loss_workspace(d.bn, a);
+  const auto o = a.options();
+  Tensor axis = at::empty({bn, K, 3, R, C}, o), lamb = at::empty({bn, K, R, C}, o), weight = at::empty({bn, 3 * K, R, C}, o);
+  ok(A.sgr_light_heads_fwd(rp(ax), rp(la), rp(we), wp(axis), wp(lamb), wp(weight), nullptr, (int)bn, (int)K, (int)R, (int)C, st), "sgr_light_heads_fwd");
+  ok(A.sgr_render_bwd_brdf(rp(g_d), rp(g_s), rp(a), rp(n), rp(r), nullptr, rp(axis), rp(lamb), rp(weight), rp(dirs), rp(view), wp(g_alb), wp(g_nrm),
+                           wp(g_rgh), (int)bn, (int)K, (int)R, (int)C, (int)eh, (int)ew, (int)h, (int)w, (float)F0, 1, st),
+     "sgr_render_bwd_brdf");
+}
+
+// The objective on one rank -> (objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied).
+// need_grad: forward statistics pass -> render loss (3 launches, value included; the third also writes ren_w * d renderErr / d{diffuse, spec})
+// -> the objective's backward pass (SG gradients + reconstruction numerator + the scalar tail in its fold): ten launches, eight of them
+// small.  !need_grad (forward-only callers): the last pass runs without its gradient half (NULL gradient outputs) and the render-loss
+// backward is skipped; the gradient outputs are absent.  `want` (implies need_grad): the BRDF maps' gradients follow, at the maps'
+// resolution (1x or 2x the env grid); the C ABI writes the three together, the ones not wanted are dropped.
+using T12 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+T12 objective_fwdbwd(OBJ_ARGS, bool need_grad, MapWants want) {
+  ObjectivePrologue p(OBJ_INPUTS_PASS);
+  const Api& A = api();
+  const auto& o = p.o;
+  const auto& d = p.d;
+  Tensor parts_r = at::empty({2}, o), parts_b = at::empty({2}, o), scale_r = at::empty({1}, o);
   Tensor objective = at::empty({}, o), render_err = at::empty({}, o), recon_err = at::empty({}, o);
   handoff = handoff && !heads && need_grad;
   const int pm = heads ? 3 : 1;      // 3: axis / lamb / weight are the decoders' last-convolution outputs (heads as the kernels' prologue)
-  Tensor lam_t = handoff ? at::empty_like(la) : Tensor(), w_t = handoff ? at::empty_like(we) : Tensor();      // post-tan values: forward writes, backward reads (premap 2)
-  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
-  // forward half in four launches (ABI 5): the statistics kernel (it pools the object mask itself: the env mask needs it before the render-loss
-  // pass produces it), then the render loss's three passes -- the first also folds the env statistics per image, the third also writes
-  // ren_w * d renderErr / d{diffuse, spec} when gradients are wanted (no fold launch, no loss_bwd launch between the two heavy kernels)
-  Tensor g_axis = none_like(a), g_lamb = none_like(a), g_weight = none_like(a), applied = none_like(a), g_d, g_s;
+  Tensor lam_t = handoff ? at::empty_like(p.la) : Tensor(), w_t = handoff ? at::empty_like(p.we) : Tensor();      // post-tan values: forward writes, backward reads (premap 2)
+  Tensor g_axis, g_lamb, g_weight, applied, g_d, g_s, g_alb, g_nrm, g_rgh;
   if (need_grad) {
-    g_axis = at::empty_like(ax); g_lamb = at::empty_like(la); g_weight = at::empty_like(we); applied = at::empty({2}, o);
-    g_d = at::empty_like(diffuse); g_s = at::empty_like(spec);
+    g_axis = at::empty_like(p.ax); g_lamb = at::empty_like(p.la); g_weight = at::empty_like(p.we); applied = at::empty({2}, o);
+    g_d = at::empty_like(p.diffuse); g_s = at::empty_like(p.spec);
   }
-  ok(A.sgr_light_objective_fwd(rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), rp(gt), rp(i), rp(sg), rp(ind), wp(lam_t), wp(w_t), wp(diffuse), wp(spec),
-                               wp(mask), wp(coef), wp(im_s), wp(seg_s), wp(rendered), wp(coef_ds), wp(parts_r), render_err.data_ptr<float>(), wp(scale_r), (float)ren_w,
-                               wp(g_d), wp(g_s), wp(ws), wp(ws_r), bn, K, R, C, (int)eh, (int)ew, (int)d.imH, (int)d.imW, (int)d.h, (int)d.w, (float)F0, pm, st),
+  if (want.any()) { g_alb = at::empty_like(p.a); g_nrm = at::empty_like(p.n); g_rgh = at::empty_like(p.r); }
+  // forward half in four launches: the statistics kernel (it pools the object mask itself: the env mask needs it before the render-loss pass
+  // produces it), then the render loss's three passes -- the first also folds the env statistics per image
+  ok(A.sgr_light_objective_fwd(rp(p.a), rp(p.n), rp(p.r), rp(p.ax), rp(p.la), rp(p.we), rp(p.dirs), rp(p.view), rp(p.gt), rp(p.i), rp(p.sg), rp(p.ind), wp(lam_t),
+                               wp(w_t), wp(p.diffuse), wp(p.spec), wp(p.mask), wp(p.coef), wp(p.im_s), wp(p.seg_s), wp(p.rendered), wp(p.coef_ds), wp(parts_r),
+                               render_err.data_ptr<float>(), wp(scale_r), (float)ren_w, wp(g_d), wp(g_s), wp(p.ws), wp(p.ws_r), p.bn, p.K, p.R, p.C, (int)eh, (int)ew,
+                               (int)d.imH, (int)d.imW, (int)d.h, (int)d.w, (float)F0, pm, p.st),
      "sgr_light_objective_fwd");
-  ok(A.sgr_fused_bwd_recon_total(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
-                                 rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), wp(parts_b), wp(ws), bn, K, R, C, (int)eh, (int)ew, (int)d.h, (int)d.w,
-                                 (float)F0, handoff ? 2 : pm, (float)offset, (float)rec_w, rp(render_err), (float)ren_w, objective.data_ptr<float>(),
-                                 recon_err.data_ptr<float>(), wp(applied), st),
-     "sgr_fused_bwd_recon");
-  return {objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, applied};
+  ok(A.sgr_fused_bwd_recon_total_brdf(rp(p.a), rp(p.n), rp(p.r), rp(p.ax), handoff ? rp(lam_t) : rp(p.la), handoff ? rp(w_t) : rp(p.we), rp(p.dirs), rp(p.view), rp(p.gt),
+                                      rp(p.mask), rp(p.coef), rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb),
+                                      heads ? nullptr : wp(g_nrm), heads ? nullptr : wp(g_rgh), wp(parts_b), wp(p.ws), p.bn, p.K, p.R, p.C, (int)eh, (int)ew, (int)d.h,
+                                      (int)d.w, (float)F0, handoff ? 2 : pm, (float)offset, (float)rec_w, rp(render_err), (float)ren_w, objective.data_ptr<float>(),
+                                      recon_err.data_ptr<float>(), wp(applied), p.st),
+     want.any() ? "sgr_fused_bwd_recon_brdf" : "sgr_fused_bwd_recon");
+  if (heads && want.any()) heads_brdf_pass(p.ax, p.la, p.we, p.a, p.n, p.r, g_d, g_s, p.dirs, p.view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, d.h, d.w, F0, p.st);
+  return {objective, render_err, recon_err, p.rendered, p.coef, g_axis, g_lamb, g_weight, want.albedo ? g_alb : Tensor(), want.normal ? g_nrm : Tensor(),
+          want.rough ? g_rgh : Tensor(), applied};
 }
-T9 light_objective_fwdbwd_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                               const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double, double, Cam, double,
-                               double, double, bool, bool, bool need_grad) {
+T12 objective_fwdbwd_shapes(OBJ_ARGS, bool need_grad, MapWants want) {
   const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
   const auto o = albedo.options();
-  auto g = [&](const Tensor& t) { return need_grad ? at::empty(t.sizes(), t.options()) : none_like(albedo); };
-  return {at::empty({}, o), at::empty({}, o), at::empty({}, o), at::empty({d.bn, 3, d.R, d.C}, o), at::empty({d.bn}, o), g(axis), g(lamb), g(weight),
-          need_grad ? at::empty({2}, o) : none_like(albedo)};
+  auto g = [&](const Tensor& t, bool wanted) { return wanted ? at::empty(t.sizes(), o) : Tensor(); };
+  return {at::empty({}, o), at::empty({}, o), at::empty({}, o), at::empty({d.bn, 3, d.R, d.C}, o), at::empty({d.bn}, o), g(axis, need_grad), g(lamb, need_grad),
+          g(weight, need_grad), g(albedo, want.albedo), g(normal, want.normal), g(rough, want.rough), need_grad ? at::empty({2}, o) : Tensor()};
 }
-using ObjSig = T9(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                  int64_t, int64_t, double, double, Cam, double, double, double, bool, bool, bool);
+
+// light_objective_fwdbwd(...) -> (objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, applied): SG gradients only
+using T9 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+T9 light_objective_fwdbwd_cuda(OBJ_ARGS, bool need_grad) { return pick<0, 1, 2, 3, 4, 5, 6, 7, 11>(objective_fwdbwd(OBJ_PASS, need_grad, MapWants{}), albedo); }
+T9 light_objective_fwdbwd_meta(OBJ_ARGS, bool need_grad) { return pick<0, 1, 2, 3, 4, 5, 6, 7, 11>(objective_fwdbwd_shapes(OBJ_PASS, need_grad, MapWants{}), albedo); }
+// light_objective_brdf_fwdbwd(...) -> the twelve: always the gradient half; g_albedo / g_normal / g_rough empty where not wanted
+T12 light_objective_brdf_fwdbwd_cuda(OBJ_ARGS, bool want_albedo, bool want_normal, bool want_rough) {
+  return pick<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11>(objective_fwdbwd(OBJ_PASS, true, MapWants{want_albedo, want_normal, want_rough}), albedo);
+}
+T12 light_objective_brdf_fwdbwd_meta(OBJ_ARGS, bool want_albedo, bool want_normal, bool want_rough) {
+  return pick<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11>(objective_fwdbwd_shapes(OBJ_PASS, true, MapWants{want_albedo, want_normal, want_rough}), albedo);
+}
+using ObjSig = T9(OBJ_ARGS, bool);
+using ObjBrdfSig = T12(OBJ_ARGS, bool, bool, bool);
+using ObjPlainSig = T5(OBJ_ARGS);
 
 // light_objective(...) -> (objective, renderErr, reconstErr, renderedImPred, envScale); differentiable w.r.t. the SG parameters only
-T5 light_objective_backend(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& im,
-                           const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam, double ren_w,
-                           double rec_w, double offset, bool heads, bool handoff) {
+T5 light_objective_backend(OBJ_ARGS) {
   static auto op = find_op<ObjSig>("sgrender::light_objective_fwdbwd");
-  auto o = op.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff, false);
+  auto o = op.call(OBJ_PASS, false);
   return {std::get<0>(o), std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<4>(o)};
 }
-T5 light_objective_autograd(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& im,
-                            const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam, double ren_w,
-                            double rec_w, double offset, bool heads, bool handoff) {
+T5 light_objective_autograd(OBJ_ARGS) {
   const bool grad_mode = at::GradMode::is_enabled();
   TORCH_CHECK(!(grad_mode && (albedo.requires_grad() || normal.requires_grad() || rough.requires_grad() || im.requires_grad() || seg.requires_grad() ||
                               env_gt.requires_grad() || env_ind.requires_grad())),
@@ -1094,10 +1102,32 @@ T5 light_objective_autograd(const Tensor& albedo, const Tensor& normal, const Te
   {
     at::AutoDispatchBelowADInplaceOrView guard;
     static auto op = find_op<ObjSig>("sgrender::light_objective_fwdbwd");
-    o = op.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff, need);
+    o = op.call(OBJ_PASS, need);
   }
   Tensor objective = std::get<0>(o);
-  if (need) objective = PrecomputedGradsFn::apply(objective, axis, lamb, weight, std::get<5>(o), std::get<6>(o), std::get<7>(o), std::get<8>(o));
+  if (need) objective = attach_grads_autograd(objective, axis, lamb, weight, std::get<5>(o), std::get<6>(o), std::get<7>(o), std::get<8>(o));
+  return {objective, std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<4>(o)};
+}
+// light_objective_brdf(...): light_objective differentiable w.r.t. the BRDF maps as well.  No grad-requiring map (or no grad mode): exactly
+// the light_objective operator (its launches, its node); the image-side inputs are still refused.
+T5 light_objective_brdf_autograd(OBJ_ARGS) {
+  const bool grad_mode = at::GradMode::is_enabled();
+  TORCH_CHECK(!(grad_mode && (im.requires_grad() || seg.requires_grad() || env_gt.requires_grad() || env_ind.requires_grad())),
+              "sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only (imBatch, segBRDFBatch, envmapsBatch and "
+              "envmapsIndBatch must not require grad)");
+  const bool wa = grad_mode && albedo.requires_grad(), wn = grad_mode && normal.requires_grad(), wr = grad_mode && rough.requires_grad();
+  if (!(wa || wn || wr)) {
+    static auto plain = find_op<ObjPlainSig>("sgrender::light_objective");
+    return plain.call(OBJ_PASS);
+  }
+  T12 o;
+  {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = find_op<ObjBrdfSig>("sgrender::light_objective_brdf_fwdbwd");
+    o = op.call(OBJ_PASS, wa, wn, wr);
+  }
+  Tensor objective = PrecomputedGradsFn::apply(std::get<0>(o), axis, lamb, weight, albedo, normal, rough, std::get<5>(o), std::get<6>(o), std::get<7>(o), std::get<8>(o),
+                                               std::get<9>(o), std::get<10>(o), std::get<11>(o));
   return {objective, std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<4>(o)};
 }
 
@@ -1125,40 +1155,25 @@ void check_stage1_tensors(int64_t bn, int64_t R, int64_t C, const Tensor& mask, 
 
 // ---- the same objective under batch sharding: three stage operators with the two collectives between them ----
 // stage 1: forward statistics pass + render-loss passes -> sums = [num_r, den_r, 0, den_e] for ONE all-reduce before the backward pass
-using T12 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
-T12 light_objective_stage1_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam,
-                                bool heads, bool handoff) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind});
-  const c10::DeviceGuard guard(dev);
-  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const Tensor i = im.contiguous(), sg = seg.contiguous(), gt = env_gt.contiguous(), ind = env_ind.contiguous().reshape({-1});
-  const auto d = check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew);
-  const auto o = a.options();
+T12 light_objective_stage1_cuda(OBJ_INPUTS, bool heads, bool handoff) {
+  ObjectivePrologue p(OBJ_INPUTS_PASS);
   const Api& A = api();
-  void* st = stream_of(dev);
-  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
-  Tensor diffuse = at::empty({d.bn, 3, d.R, d.C}, o), spec = at::empty({d.bn, 3, d.R, d.C}, o), im_s = at::empty({d.bn, 3, d.R, d.C}, o);
-  Tensor seg_s = at::empty({d.bn, 1, d.R, d.C}, o), rendered = at::empty({d.bn, 3, d.R, d.C}, o), mask = at::empty({d.bn, d.R * d.C}, o), coef = at::empty({d.bn}, o);
-  Tensor coef_ds = at::empty({d.bn, 2}, o), sums = at::empty({4}, o);
-  TORCH_CHECK(A.sgr_fused_recon_workspace_floats(bn, R, C) == recon_workspace_floats(d.bn, d.R, d.C), "sgrender: workspace size disagrees with the kernel library");
-  Tensor ws = at::empty({recon_workspace_floats(d.bn, d.R, d.C)}, o), ws_r = loss_workspace(d.bn, a);
+  const auto& d = p.d;
+  TORCH_CHECK(p.ws.numel() == recon_workspace_floats(d.bn, d.R, d.C), "sgrender: workspace size disagrees with the kernel library");
+  Tensor sums = at::empty({4}, p.o);
   handoff = handoff && !heads;
-  Tensor lam_t = handoff ? at::empty_like(la) : none_like(a), w_t = handoff ? at::empty_like(we) : none_like(a);
-  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
+  Tensor lam_t = handoff ? at::empty_like(p.la) : none_like(p.a), w_t = handoff ? at::empty_like(p.we) : none_like(p.a);
   float* sp = sums.data_ptr<float>();
-  ok(A.sgr_fused_fwd_recon_seg(rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), rp(gt), rp(sg), (int)d.imH, (int)d.imW, rp(ind), wp(lam_t), wp(w_t),
-                               wp(diffuse), wp(spec), wp(mask), wp(coef), sp + 2 /* (0, env-mask sum) */, wp(ws), bn, K, R, C, (int)eh, (int)ew, (int)d.h, (int)d.w,
-                               (float)F0, heads ? 3 : 1, st),
+  ok(A.sgr_fused_fwd_recon_seg(rp(p.a), rp(p.n), rp(p.r), rp(p.ax), rp(p.la), rp(p.we), rp(p.dirs), rp(p.view), rp(p.gt), rp(p.sg), (int)d.imH, (int)d.imW, rp(p.ind),
+                               wp(lam_t), wp(w_t), wp(p.diffuse), wp(p.spec), wp(p.mask), wp(p.coef), sp + 2 /* (0, env-mask sum) */, wp(p.ws), p.bn, p.K, p.R, p.C,
+                               (int)eh, (int)ew, (int)d.h, (int)d.w, (float)F0, heads ? 3 : 1, p.st),
      "sgr_fused_fwd_recon");
-  ok(A.sgr_render_loss_fwd_total(rp(diffuse), rp(spec), rp(i), rp(sg), wp(im_s), wp(seg_s), wp(rendered), wp(coef_ds), sp /* (num_r, den_r) */, nullptr, nullptr, 3.0f,
-                                 wp(ws_r), bn, R, C, (int)d.imH, (int)d.imW, st),
+  ok(A.sgr_render_loss_fwd_total(rp(p.diffuse), rp(p.spec), rp(p.i), rp(p.sg), wp(p.im_s), wp(p.seg_s), wp(p.rendered), wp(p.coef_ds), sp /* (num_r, den_r) */, nullptr,
+                                 nullptr, 3.0f, wp(p.ws_r), p.bn, p.R, p.C, (int)d.imH, (int)d.imW, p.st),
      "sgr_render_loss_fwd");
-  return {diffuse, spec, mask, coef, im_s, seg_s, rendered, coef_ds, sums, ws, lam_t, w_t};
+  return {p.diffuse, p.spec, p.mask, p.coef, p.im_s, p.seg_s, p.rendered, p.coef_ds, sums, p.ws, lam_t, w_t};
 }
-T12 light_objective_stage1_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double, double, Cam, bool heads,
-                                bool handoff) {
+T12 light_objective_stage1_meta(OBJ_INPUTS, bool heads, bool handoff) {
   const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
   const auto o = albedo.options();
   const bool h = handoff && !heads;
@@ -1166,12 +1181,18 @@ T12 light_objective_stage1_meta(const Tensor& albedo, const Tensor& normal, cons
   return {img(), img(), at::empty({d.bn, d.R * d.C}, o), at::empty({d.bn}, o), img(), at::empty({d.bn, 1, d.R, d.C}, o), img(), at::empty({d.bn, 2}, o), at::empty({4}, o),
           at::empty({recon_workspace_floats(d.bn, d.R, d.C)}, o), h ? at::empty(lamb.sizes(), o) : none_like(albedo), h ? at::empty(weight.sizes(), o) : none_like(albedo)};
 }
+
 // stage 2 (sums = the rank-summed vector): render-loss value + backward with the global normaliser, the objective's backward pass
-// with the global env-mask sum -> (render_err, g_axis, g_lamb, g_weight, parts_b = (num_e of this shard, its mask sum))
-T5 light_objective_stage2_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                               const Tensor& env_gt, const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
-                               const Tensor& seg_s, const Tensor& coef_ds, const Tensor& sums, Tensor& ws /* written: schema Tensor(a!) */, const Tensor& lam_t, const Tensor& w_t, int64_t eh,
-                               int64_t ew, double fov, double F0, Cam cam, double ren_w, double rec_w, double offset, bool heads, bool need_grad) {
+// with the global env-mask sum -> (render_err, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, parts_b = (num_e of this shard, its
+// mask sum)); need_grad and `want` as in objective_fwdbwd
+#define STAGE2_ARGS                                                                                                                                          \
+  const Tensor &albedo, const Tensor &normal, const Tensor &rough, const Tensor &axis, const Tensor &lamb, const Tensor &weight, const Tensor &env_gt,          \
+      const Tensor &mask, const Tensor &coef, const Tensor &diffuse, const Tensor &spec, const Tensor &im_s, const Tensor &seg_s, const Tensor &coef_ds,        \
+      const Tensor &sums, Tensor &ws /* written: schema Tensor(a!) */, const Tensor &lam_t, const Tensor &w_t, int64_t eh, int64_t ew, double fov, double F0,   \
+      Cam cam, double ren_w, double rec_w, double offset, bool heads
+#define STAGE2_PASS \
+  albedo, normal, rough, axis, lamb, weight, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads
+T8 objective_stage2(STAGE2_ARGS, bool need_grad, MapWants want) {
   const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws});
   const c10::DeviceGuard guard(dev);
   const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
@@ -1190,30 +1211,43 @@ T5 light_objective_stage2_cuda(const Tensor& albedo, const Tensor& normal, const
   Tensor render_err = at::empty({}, o), scale_r = at::empty({1}, o), parts_b = at::empty({2}, o);
   const float* sp = sums.const_data_ptr<float>();
   ok(A.sgr_loss_finalize(sp, render_err.data_ptr<float>(), wp(scale_r), 3.0f, st), "sgr_loss_finalize");
-  Tensor g_axis = none_like(a), g_lamb = none_like(a), g_weight = none_like(a), g_d, g_s;
+  Tensor g_axis, g_lamb, g_weight, g_d, g_s, g_alb, g_nrm, g_rgh;
   if (need_grad) {
     g_axis = at::empty_like(ax); g_lamb = at::empty_like(la); g_weight = at::empty_like(we);
     g_d = at::empty_like(diffuse); g_s = at::empty_like(spec);
+    if (want.any()) { g_alb = at::empty_like(a); g_nrm = at::empty_like(n); g_rgh = at::empty_like(r); }
     ok(A.sgr_render_loss_bwd_scaled(nullptr, (float)ren_w, rp(scale_r), rp(diffuse), rp(spec), rp(im_s), rp(seg_s), rp(coef_ds), wp(g_d), wp(g_s), bn, R, C, st),
        "sgr_render_loss_bwd");
   }
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
-  ok(A.sgr_fused_bwd_recon(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
-                           sp + 3 /* the global env-mask sum */, rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), wp(parts_b), ws.mutable_data_ptr<float>(), bn, K, R,
-                           C, (int)eh, (int)ew, (int)b.h, (int)b.w, (float)F0, handoff ? 2 : (heads ? 3 : 1), (float)offset, (float)rec_w, st),
-     "sgr_fused_bwd_recon");
-  return {render_err, g_axis, g_lamb, g_weight, parts_b};
+  ok(A.sgr_fused_bwd_recon_brdf(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
+                                sp + 3 /* the global env-mask sum */, rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb),
+                                heads ? nullptr : wp(g_nrm), heads ? nullptr : wp(g_rgh), wp(parts_b), ws.mutable_data_ptr<float>(), bn, K, R, C, (int)eh, (int)ew,
+                                (int)b.h, (int)b.w, (float)F0, handoff ? 2 : (heads ? 3 : 1), (float)offset, (float)rec_w, st),
+     want.any() ? "sgr_fused_bwd_recon_brdf" : "sgr_fused_bwd_recon");
+  if (heads && want.any()) heads_brdf_pass(ax, la, we, a, n, r, g_d, g_s, dirs, view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, b.h, b.w, F0, st);
+  return {render_err, g_axis, g_lamb, g_weight, want.albedo ? g_alb : Tensor(), want.normal ? g_nrm : Tensor(), want.rough ? g_rgh : Tensor(), parts_b};
 }
-T5 light_objective_stage2_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor&,
-                               const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s, const Tensor& seg_s, const Tensor& coef_ds,
-                               const Tensor& sums, Tensor& ws, const Tensor&, const Tensor&, int64_t, int64_t, double, double, Cam, double, double, double, bool, bool need_grad) {
+T8 objective_stage2_shapes(STAGE2_ARGS, bool need_grad, MapWants want) {
   const auto d = check_sg(axis, lamb, weight);
   check_brdf(albedo, normal, rough);
   check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
   const auto o = albedo.options();
-  auto g = [&](const Tensor& t) { return need_grad ? at::empty(t.sizes(), o) : none_like(albedo); };
-  return {at::empty({}, o), g(axis), g(lamb), g(weight), at::empty({2}, o)};
+  auto g = [&](const Tensor& t, bool wanted) { return wanted ? at::empty(t.sizes(), o) : Tensor(); };
+  return {at::empty({}, o), g(axis, need_grad), g(lamb, need_grad), g(weight, need_grad), g(albedo, want.albedo), g(normal, want.normal), g(rough, want.rough),
+          at::empty({2}, o)};
 }
+// light_objective_stage2(..., need_grad) -> (render_err, g_axis, g_lamb, g_weight, parts_b); light_objective_stage2_brdf(..., want_*) -> all
+// eight, always the gradient half
+T5 light_objective_stage2_cuda(STAGE2_ARGS, bool need_grad) { return pick<0, 1, 2, 3, 7>(objective_stage2(STAGE2_PASS, need_grad, MapWants{}), albedo); }
+T5 light_objective_stage2_meta(STAGE2_ARGS, bool need_grad) { return pick<0, 1, 2, 3, 7>(objective_stage2_shapes(STAGE2_PASS, need_grad, MapWants{}), albedo); }
+T8 light_objective_stage2_brdf_cuda(STAGE2_ARGS, bool want_albedo, bool want_normal, bool want_rough) {
+  return pick<0, 1, 2, 3, 4, 5, 6, 7>(objective_stage2(STAGE2_PASS, true, MapWants{want_albedo, want_normal, want_rough}), albedo);
+}
+T8 light_objective_stage2_brdf_meta(STAGE2_ARGS, bool want_albedo, bool want_normal, bool want_rough) {
+  return pick<0, 1, 2, 3, 4, 5, 6, 7>(objective_stage2_shapes(STAGE2_PASS, true, MapWants{want_albedo, want_normal, want_rough}), albedo);
+}
+
 // stage 3 (num_e = the rank-summed reconstruction numerator): the objective's scalar tail
 T2 light_objective_stage3_cuda(const Tensor& render_err, const Tensor& num_e, const Tensor& sums, double ren_w, double rec_w, int64_t eh, int64_t ew) {
   const auto dev = require_hip({&render_err, &num_e, &sums});
@@ -1231,227 +1265,6 @@ T2 light_objective_stage3_cuda(const Tensor& render_err, const Tensor& num_e, co
 T2 light_objective_stage3_meta(const Tensor& render_err, const Tensor&, const Tensor&, double, double, int64_t, int64_t) {
   return {at::empty({}, render_err.options()), at::empty({}, render_err.options())};
 }
-
-// ---- the objective with gradients w.r.t. the BRDF maps as well (light_objective(..., brdf_grads=True)) ----------------------------
-// The same launches as light_objective_fwdbwd / light_objective_stage2, then the render layer's BRDF backward from the SG lobes driven by the
-// render cotangents those already hold (sgr_fused_bwd_recon_total_brdf / sgr_fused_bwd_recon_brdf); a map that is not asked for gets no
-// output (an empty tensor).
-// Six precomputed gradients: the SG trio and the three maps, scaled by the incoming cotangent exactly like the trio (two launches of
-// sgr_rescale_inplace_flip with the same parity: each reads applied2[parity] and writes the new factor to the other slot).
-void rescale_grads6_cuda(Tensor& g_axis, Tensor& g_lamb, Tensor& g_weight, Tensor& g_albedo, Tensor& g_normal, Tensor& g_rough, const Tensor& scale,
-                         Tensor& applied, int64_t parity) {
-  const auto dev = require_hip({&g_axis, &g_lamb, &g_weight, &scale, &applied});
-  const c10::DeviceGuard guard(dev);
-  TORCH_CHECK(g_axis.is_contiguous() && g_lamb.is_contiguous() && g_weight.is_contiguous() && applied.numel() == 2 && scale.numel() == 1, "sgrender: rescale_grads6_ arguments");
-  const Tensor sc = scale.contiguous();
-  float* xs[3] = {g_axis.data_ptr<float>(), g_lamb.data_ptr<float>(), g_weight.data_ptr<float>()};
-  long long ns[3] = {(long long)g_axis.numel(), (long long)g_lamb.numel(), (long long)g_weight.numel()};
-  ok(api().sgr_rescale_inplace_flip(xs, ns, 3, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
-  int nb = 0;
-  for (Tensor* t : {&g_albedo, &g_normal, &g_rough}) {
-    if (!present(*t)) continue;
-    TORCH_CHECK(t->is_contiguous() && t->device() == dev, "sgrender: rescale_grads6_ arguments");
-    xs[nb] = t->data_ptr<float>();
-    ns[nb++] = (long long)t->numel();
-  }
-  if (nb) ok(api().sgr_rescale_inplace_flip(xs, ns, nb, rp(sc), applied.data_ptr<float>(), (int)parity, stream_of(dev)), "sgr_rescale_inplace_flip");
-}
-void rescale_grads6_meta(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t) {}
-
-struct PrecomputedGrads6Fn : public torch::autograd::Function<PrecomputedGrads6Fn> {
-  // inputs: value, axis, lamb, weight, albedo, normal, rough, then their six gradients (a map's empty when not asked for) and `applied`
-  static Tensor forward(AutogradContext* ctx, const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& albedo,
-                        const Tensor& normal, const Tensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight, const Tensor& g_albedo,
-                        const Tensor& g_normal, const Tensor& g_rough, const Tensor& applied) {
-    ctx->save_for_backward({g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied});
-    ctx->saved_data["parity"] = (int64_t)0;
-    ctx->saved_data["handed_out"] = false;
-    ctx->set_materialize_grads(false);
-    at::AutoDispatchBelowADInplaceOrView guard;
-    return value.alias();
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list g) {
-    variable_list out(14);
-    if (!g[0].defined()) return out;
-    const auto saved = ctx->get_saved_variables();
-    Tensor gs[6] = {saved[0], saved[1], saved[2], saved[3], saved[4], saved[5]};
-    Tensor applied = saved[6];
-    const int64_t parity = ctx->saved_data["parity"].toInt();
-    if (ctx->saved_data["handed_out"].toBool()) {      // a second backward through this node: as PrecomputedGradsFn
-      TORCH_CHECK(applied[parity].item<float>() != 0.0f, "sgrender: light_objective was first back-propagated with a zero cotangent; its stored "
-                  "gradients are gone -- re-evaluate the objective instead of reusing the graph");
-      const Tensor f = g[0].detach() / applied[parity];
-      for (int i = 0; i < 6; ++i)
-        if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i] * f;
-      return out;
-    }
-    ctx->saved_data["handed_out"] = true;
-    static auto op = find_op<void(Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const Tensor&, Tensor&, int64_t)>("sgrender::rescale_grads6_");
-    op.call(gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], g[0].detach().to(at::kFloat).reshape({1}), applied, parity);
-    ctx->saved_data["parity"] = (int64_t)(1 - parity);
-    for (int i = 0; i < 6; ++i)
-      if (ctx->needs_input_grad(1 + i) && present(gs[i])) out[1 + i] = gs[i];
-    return out;
-  }
-};
-Tensor attach_grads6_backend(const Tensor& value, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                             const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
-  return value.clone();
-}
-Tensor attach_grads6_autograd(const Tensor& value, const Tensor& axis, const Tensor& lamb, const Tensor& weight, const Tensor& albedo, const Tensor& normal,
-                              const Tensor& rough, const Tensor& g_axis, const Tensor& g_lamb, const Tensor& g_weight, const Tensor& g_albedo, const Tensor& g_normal,
-                              const Tensor& g_rough, const Tensor& applied) {
-  return PrecomputedGrads6Fn::apply(value, axis, lamb, weight, albedo, normal, rough, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied);
-}
-
-// Decoder outputs (heads): the BRDF backward needs the activated SG parameters -- sgr_light_heads_fwd into temporaries, then the layer's
-// BRDF backward from them (premap 1) driven by the objective's render cotangents; the SG pass itself keeps the heads as its prologue.
-void heads_brdf_pass(const Tensor& ax, const Tensor& la, const Tensor& we, const Tensor& a, const Tensor& n, const Tensor& r, const Tensor& g_d,
-                     const Tensor& g_s, const Tensor& dirs, const Tensor& view, Tensor& g_alb, Tensor& g_nrm, Tensor& g_rgh, int64_t bn, int64_t K,
-                     int64_t R, int64_t C, int64_t eh, int64_t ew, int64_t h, int64_t w, double F0, void* st) {
-  const Api& A = api();
-  const auto o = a.options();
-  Tensor axis = at::empty({bn, K, 3, R, C}, o), lamb = at::empty({bn, K, R, C}, o), weight = at::empty({bn, 3 * K, R, C}, o);
-  ok(A.sgr_light_heads_fwd(rp(ax), rp(la), rp(we), wp(axis), wp(lamb), wp(weight), nullptr, (int)bn, (int)K, (int)R, (int)C, st), "sgr_light_heads_fwd");
-  ok(A.sgr_render_bwd_brdf(rp(g_d), rp(g_s), rp(a), rp(n), rp(r), nullptr, rp(axis), rp(lamb), rp(weight), rp(dirs), rp(view), wp(g_alb), wp(g_nrm),
-                           wp(g_rgh), (int)bn, (int)K, (int)R, (int)C, (int)eh, (int)ew, (int)h, (int)w, (float)F0, 1, st),
-     "sgr_render_bwd_brdf");
-}
-
-// light_objective_brdf_fwdbwd(...) -> (objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, applied)
-// light_objective_fwdbwd(need_grad = True) followed by the BRDF maps' gradients (sgr_fused_bwd_recon_total_brdf: the objective's pass, then
-// the layer's BRDF backward from the SG lobes); g_albedo / g_normal / g_rough at the maps' resolution (1x or 2x the env grid), empty where
-// not wanted (the C ABI writes the three together)
-T12 light_objective_brdf_fwdbwd_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                     const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0,
-                                     Cam cam, double ren_w, double rec_w, double offset, bool heads, bool handoff, bool want_albedo, bool want_normal, bool want_rough) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind});
-  const c10::DeviceGuard guard(dev);
-  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const Tensor i = im.contiguous(), sg = seg.contiguous(), gt = env_gt.contiguous(), ind = env_ind.contiguous().reshape({-1});
-  const auto d = check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew);
-  const auto o = a.options();
-  const Api& A = api();
-  void* st = stream_of(dev);
-  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
-  Tensor diffuse = at::empty({d.bn, 3, d.R, d.C}, o), spec = at::empty({d.bn, 3, d.R, d.C}, o), im_s = at::empty({d.bn, 3, d.R, d.C}, o);
-  Tensor seg_s = at::empty({d.bn, 1, d.R, d.C}, o), rendered = at::empty({d.bn, 3, d.R, d.C}, o), mask = at::empty({d.bn, d.R * d.C}, o), coef = at::empty({d.bn}, o);
-  Tensor coef_ds = at::empty({d.bn, 2}, o), parts_r = at::empty({2}, o), parts_b = at::empty({2}, o), scale_r = at::empty({1}, o);
-  Tensor ws = at::empty({A.sgr_fused_recon_workspace_floats(bn, R, C)}, o), ws_r = loss_workspace(d.bn, a);
-  Tensor objective = at::empty({}, o), render_err = at::empty({}, o), recon_err = at::empty({}, o);
-  handoff = handoff && !heads;
-  const int pm = heads ? 3 : 1;
-  Tensor lam_t = handoff ? at::empty_like(la) : Tensor(), w_t = handoff ? at::empty_like(we) : Tensor();
-  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
-  Tensor g_axis = at::empty_like(ax), g_lamb = at::empty_like(la), g_weight = at::empty_like(we), applied = at::empty({2}, o);
-  Tensor g_d = at::empty_like(diffuse), g_s = at::empty_like(spec);
-  Tensor g_alb = at::empty_like(a), g_nrm = at::empty_like(n), g_rgh = at::empty_like(r);
-  ok(A.sgr_light_objective_fwd(rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), rp(gt), rp(i), rp(sg), rp(ind), wp(lam_t), wp(w_t), wp(diffuse), wp(spec),
-                               wp(mask), wp(coef), wp(im_s), wp(seg_s), wp(rendered), wp(coef_ds), wp(parts_r), render_err.data_ptr<float>(), wp(scale_r), (float)ren_w,
-                               wp(g_d), wp(g_s), wp(ws), wp(ws_r), bn, K, R, C, (int)eh, (int)ew, (int)d.imH, (int)d.imW, (int)d.h, (int)d.w, (float)F0, pm, st),
-     "sgr_light_objective_fwd");
-  ok(A.sgr_fused_bwd_recon_total_brdf(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
-                                      rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb), heads ? nullptr : wp(g_nrm),
-                                      heads ? nullptr : wp(g_rgh), wp(parts_b), wp(ws), bn, K, R, C, (int)eh, (int)ew, (int)d.h, (int)d.w, (float)F0,
-                                      handoff ? 2 : pm, (float)offset, (float)rec_w, rp(render_err), (float)ren_w, objective.data_ptr<float>(),
-                                      recon_err.data_ptr<float>(), wp(applied), st),
-     "sgr_fused_bwd_recon_brdf");
-  if (heads) heads_brdf_pass(ax, la, we, a, n, r, g_d, g_s, dirs, view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, d.h, d.w, F0, st);
-  return {objective, render_err, recon_err, rendered, coef, g_axis, g_lamb, g_weight, want_albedo ? g_alb : none_like(a), want_normal ? g_nrm : none_like(a),
-          want_rough ? g_rgh : none_like(a), applied};
-}
-T12 light_objective_brdf_fwdbwd_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                     const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double, double, Cam, double,
-                                     double, double, bool, bool, bool want_albedo, bool want_normal, bool want_rough) {
-  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
-  const auto o = albedo.options();
-  auto g = [&](const Tensor& t, bool want) { return want ? at::empty(t.sizes(), o) : none_like(albedo); };
-  return {at::empty({}, o), at::empty({}, o), at::empty({}, o), at::empty({d.bn, 3, d.R, d.C}, o), at::empty({d.bn}, o), g(axis, true), g(lamb, true), g(weight, true),
-          g(albedo, want_albedo), g(normal, want_normal), g(rough, want_rough), at::empty({2}, o)};
-}
-using ObjBrdfSig = T12(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                       const Tensor&, int64_t, int64_t, double, double, Cam, double, double, double, bool, bool, bool, bool, bool);
-using ObjPlainSig = T5(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                       const Tensor&, int64_t, int64_t, double, double, Cam, double, double, double, bool, bool);
-
-// light_objective_brdf(...): light_objective differentiable w.r.t. the BRDF maps as well.  No grad-requiring map (or no grad mode): exactly
-// the light_objective operator (its launches, its node); the image-side inputs are still refused.
-T5 light_objective_brdf_autograd(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                 const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, double fov, double F0, Cam cam,
-                                 double ren_w, double rec_w, double offset, bool heads, bool handoff) {
-  const bool grad_mode = at::GradMode::is_enabled();
-  TORCH_CHECK(!(grad_mode && (im.requires_grad() || seg.requires_grad() || env_gt.requires_grad() || env_ind.requires_grad())),
-              "sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only (imBatch, segBRDFBatch, envmapsBatch and "
-              "envmapsIndBatch must not require grad)");
-  const bool wa = grad_mode && albedo.requires_grad(), wn = grad_mode && normal.requires_grad(), wr = grad_mode && rough.requires_grad();
-  if (!(wa || wn || wr)) {
-    static auto plain = find_op<ObjPlainSig>("sgrender::light_objective");
-    return plain.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff);
-  }
-  T12 o;
-  {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = find_op<ObjBrdfSig>("sgrender::light_objective_brdf_fwdbwd");
-    o = op.call(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, handoff, wa, wn, wr);
-  }
-  Tensor objective = PrecomputedGrads6Fn::apply(std::get<0>(o), axis, lamb, weight, albedo, normal, rough, std::get<5>(o), std::get<6>(o), std::get<7>(o), std::get<8>(o),
-                                                std::get<9>(o), std::get<10>(o), std::get<11>(o));
-  return {objective, std::get<1>(o), std::get<2>(o), std::get<3>(o), std::get<4>(o)};
-}
-
-// stage 2 with the BRDF maps' gradients: (render_err, g_axis, g_lamb, g_weight, g_albedo, g_normal, g_rough, parts_b); always the gradient half
-using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
-T8 light_objective_stage2_brdf_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                    const Tensor& env_gt, const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
-                                    const Tensor& seg_s, const Tensor& coef_ds, const Tensor& sums, Tensor& ws, const Tensor& lam_t, const Tensor& w_t, int64_t eh,
-                                    int64_t ew, double fov, double F0, Cam cam, double ren_w, double rec_w, double offset, bool heads, bool want_albedo,
-                                    bool want_normal, bool want_rough) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws});
-  const c10::DeviceGuard guard(dev);
-  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const Tensor gt = env_gt.contiguous();
-  const auto d = check_sg(ax, la, we);
-  const auto b = check_brdf(a, n, r);
-  TORCH_CHECK(sums.is_contiguous() && sums.numel() == 4 && mask.is_contiguous() && coef.is_contiguous() && diffuse.is_contiguous() && spec.is_contiguous() &&
-                  im_s.is_contiguous() && seg_s.is_contiguous() && coef_ds.is_contiguous() && ws.is_contiguous(), "sgrender: light_objective_stage2 takes stage 1's tensors as they are");
-  check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
-  TORCH_CHECK(gt.numel() == d.bn * 3 * d.R * d.C * eh * ew, "sgrender: light_objective_stage2: env_gt must be [bn,3,R,C,eh,ew], got ", gt.sizes());
-  const auto o = a.options();
-  const Api& A = api();
-  void* st = stream_of(dev);
-  const int bn = (int)d.bn, K = (int)d.K, R = (int)d.R, C = (int)d.C;
-  const bool handoff = present(lam_t) && present(w_t);
-  Tensor render_err = at::empty({}, o), scale_r = at::empty({1}, o), parts_b = at::empty({2}, o);
-  const float* sp = sums.const_data_ptr<float>();
-  ok(A.sgr_loss_finalize(sp, render_err.data_ptr<float>(), wp(scale_r), 3.0f, st), "sgr_loss_finalize");
-  Tensor g_axis = at::empty_like(ax), g_lamb = at::empty_like(la), g_weight = at::empty_like(we), g_d = at::empty_like(diffuse), g_s = at::empty_like(spec);
-  Tensor g_alb = at::empty_like(a), g_nrm = at::empty_like(n), g_rgh = at::empty_like(r);
-  ok(A.sgr_render_loss_bwd_scaled(nullptr, (float)ren_w, rp(scale_r), rp(diffuse), rp(spec), rp(im_s), rp(seg_s), rp(coef_ds), wp(g_d), wp(g_s), bn, R, C, st),
-     "sgr_render_loss_bwd");
-  const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
-  ok(A.sgr_fused_bwd_recon_brdf(rp(a), rp(n), rp(r), rp(ax), handoff ? rp(lam_t) : rp(la), handoff ? rp(w_t) : rp(we), rp(dirs), rp(view), rp(gt), rp(mask), rp(coef),
-                                sp + 3 /* the global env-mask sum */, rp(g_d), rp(g_s), wp(g_axis), wp(g_lamb), wp(g_weight), heads ? nullptr : wp(g_alb),
-                                heads ? nullptr : wp(g_nrm), heads ? nullptr : wp(g_rgh), wp(parts_b), ws.mutable_data_ptr<float>(), bn, K, R, C, (int)eh, (int)ew,
-                                (int)b.h, (int)b.w, (float)F0, handoff ? 2 : (heads ? 3 : 1), (float)offset, (float)rec_w, st),
-     "sgr_fused_bwd_recon_brdf");
-  if (heads) heads_brdf_pass(ax, la, we, a, n, r, g_d, g_s, dirs, view, g_alb, g_nrm, g_rgh, d.bn, d.K, d.R, d.C, eh, ew, b.h, b.w, F0, st);
-  return {render_err, g_axis, g_lamb, g_weight, want_albedo ? g_alb : none_like(a), want_normal ? g_nrm : none_like(a), want_rough ? g_rgh : none_like(a),
-          parts_b};
-}
-T8 light_objective_stage2_brdf_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                                    const Tensor&, const Tensor& mask, const Tensor& coef, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
-                                    const Tensor& seg_s, const Tensor& coef_ds, const Tensor& sums, Tensor& ws, const Tensor&, const Tensor&, int64_t, int64_t, double,
-                                    double, Cam, double, double, double, bool, bool want_albedo, bool want_normal, bool want_rough) {
-  const auto d = check_sg(axis, lamb, weight);
-  check_brdf(albedo, normal, rough);
-  check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
-  const auto o = albedo.options();
-  auto g = [&](const Tensor& t, bool want) { return want ? at::empty(t.sizes(), o) : none_like(albedo); };
-  return {at::empty({}, o), g(axis, true), g(lamb, true), g(weight, true), g(albedo, want_albedo), g(normal, want_normal), g(rough, want_rough), at::empty({2}, o)};
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-void no_cpu_path(const c10::OperatorHandle&, torch::jit::Stack*) { TORCH_CHECK(false, kNoCpu); }
 
 }  // namespace
 
@@ -1711,12 +1524,10 @@ TORCH_LIBRARY_IMPL(sgrender, Autograd, m) {
   m.impl("light_objective_brdf", &light_objective_brdf_autograd);
 }
 
-// no CPU path: every operator raises on CPU tensors (a namespace cannot carry a backend fallback, hence one registration each)
 TORCH_LIBRARY_IMPL(sgrender, CPU, m) {
-  for (const char* name : {"sg_to_env", "sg_to_env_bwd", "render_env", "render_env_bwd_env", "render_bwd_brdf", "fused_render", "fused_render_bwd_sg", "lsregress_coef",
-                           "lsregress_diffspec_coef", "render_loss", "render_loss_bwd", "render_loss_finalize", "recon_loss_parts", "recon_loss_bwd", "light_heads", "light_heads_bwd", "sg_shading",
-                           "light_albedo_scale", "light_encoder_input", "rescale_grads_", "attach_grads", "light_objective_fwdbwd", "light_objective",
-                           "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "allreduce_sum_", "rescale_grads6_", "attach_grads6",
-                           "light_objective_brdf_fwdbwd", "light_objective_brdf", "light_objective_stage2_brdf"})
-    m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_path>());
+  register_no_cpu(m, {"sg_to_env", "sg_to_env_bwd", "render_env", "render_env_bwd_env", "render_bwd_brdf", "fused_render", "fused_render_bwd_sg", "lsregress_coef",
+                      "lsregress_diffspec_coef", "render_loss", "render_loss_bwd", "render_loss_finalize", "recon_loss_parts", "recon_loss_bwd", "light_heads",
+                      "light_heads_bwd", "sg_shading", "light_albedo_scale", "light_encoder_input", "rescale_grads_", "attach_grads", "light_objective_fwdbwd",
+                      "light_objective", "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "allreduce_sum_", "rescale_grads6_",
+                      "attach_grads6", "light_objective_brdf_fwdbwd", "light_objective_brdf", "light_objective_stage2_brdf"});
 }

@@ -9,83 +9,11 @@
 //   bilateral_solve_fwd   BilateralGrid.solve                                 BilateralGrid.py:126-153,193-198
 //   bilateral_solve_bwd   BilateralGrid.solveForGrad                          BilateralGrid.py:155-191,200-212
 //   bilateral_solve       BilateralFunction (forward + autograd node; the grid built in forward is reused in backward)
-#include <dlfcn.h>
-
-#include <cstdlib>
-#include <string>
-#include <tuple>
-
-#include <ATen/ATen.h>
-#include <ATen/core/dispatch/Dispatcher.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/csrc/autograd/custom_function.h>
-#include <torch/library.h>
-
-#include "../../include/sgrender.h"
+#include "sgr_torch_common.hpp"
 
 namespace {
 
-using at::Tensor;
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-using T2 = std::tuple<Tensor, Tensor>;
-using T7 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
-
-#define BS_API_LIST(X) X(sgr_abi_version) X(sgr_last_error) X(sgr_bs_workspace_bytes) X(sgr_bs_grid_keys) X(sgr_bs_grid_build) X(sgr_bs_solve_fwd) X(sgr_bs_solve_bwd)
-
-struct Api {
-#define BS_DECL(name) decltype(&::name) name = nullptr;
-  BS_API_LIST(BS_DECL)
-#undef BS_DECL
-  std::string path;
-};
-
-void anchor() {}
-
-const Api& api() {
-  static const Api a = [] {
-    Api r;
-    const char* env = std::getenv("SGR_LIB");
-    if (env && env[0]) {
-      r.path = env;
-    } else {
-      Dl_info info{};
-      TORCH_CHECK(dladdr(reinterpret_cast<void*>(&anchor), &info) && info.dli_fname, "sgrender: cannot locate the torch extension on disk");
-      std::string self = info.dli_fname;
-      const auto slash = self.find_last_of('/');
-      r.path = (slash == std::string::npos ? std::string(".") : self.substr(0, slash)) + "/libsgrender.so";
-    }
-    void* h = dlopen(r.path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    TORCH_CHECK(h, "sgrender: cannot load ", r.path, " (", dlerror(), "): the HIP library has not been built.  This package has no CPU / PyTorch fallback.");
-#define BS_LOAD(name)                                                      \
-  r.name = reinterpret_cast<decltype(r.name)>(dlsym(h, #name));            \
-  TORCH_CHECK(r.name, "sgrender: ", r.path, " does not export " #name "; stale build?");
-    BS_API_LIST(BS_LOAD)
-#undef BS_LOAD
-    TORCH_CHECK(r.sgr_abi_version() == SGR_ABI_VERSION, "sgrender: ", r.path, " has ABI version ", r.sgr_abi_version(), ", this extension needs ", SGR_ABI_VERSION);
-    return r;
-  }();
-  return a;
-}
-
-void ok(int rc, const char* what) {
-  if (rc != 0) {
-    const char* msg = api().sgr_last_error();
-    TORCH_CHECK(false, "sgrender: ", what, " failed (code ", rc, "): ", msg ? msg : "");
-  }
-}
-
-constexpr const char* kNoCpu =
-    "sgrender: this layer runs only on HIP device tensors (MI355X); there is no CPU path. Move the inputs to the GPU (the reference's "
-    "isCuda=True mode).";
-
-void* stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStream(dev.index()).stream(); }
-
-template <typename Sig>
-auto find_op(const char* name) {
-  return c10::Dispatcher::singleton().findSchemaOrThrow(name, "").typed<Sig>();
-}
+using namespace sgr_host;
 
 void require_dev(std::initializer_list<const Tensor*> ts, const c10::Device& dev) {
   for (const Tensor* t : ts) {
@@ -248,8 +176,6 @@ Tensor bilateral_solve_autograd(const Tensor& image, const Tensor& pred, const T
   return BilateralSolveFn::apply(image, pred, conf, sl, sc, ss, lam, amin, tol, maxiter);
 }
 
-void no_cpu_path(const c10::OperatorHandle&, torch::jit::Stack*) { TORCH_CHECK(false, kNoCpu); }
-
 }  // namespace
 
 #define GRID_SCHEMA "Tensor pix2vert, Tensor perm, Tensor seg, Tensor nbr, Tensor nvert, Tensor m, Tensor n"
@@ -273,6 +199,4 @@ TORCH_LIBRARY_IMPL(sgrender, Meta, m) {
   m.impl("bilateral_solve", &bilateral_solve_impl);
 }
 TORCH_LIBRARY_IMPL(sgrender, Autograd, m) { m.impl("bilateral_solve", &bilateral_solve_autograd); }
-TORCH_LIBRARY_IMPL(sgrender, CPU, m) {
-  for (const char* name : {"bilateral_grid", "bilateral_solve_fwd", "bilateral_solve_bwd", "bilateral_solve"}) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_path>());
-}
+TORCH_LIBRARY_IMPL(sgrender, CPU, m) { register_no_cpu(m, {"bilateral_grid", "bilateral_solve_fwd", "bilateral_solve_bwd", "bilateral_solve"}); }

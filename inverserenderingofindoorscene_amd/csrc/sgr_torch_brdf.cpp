@@ -9,93 +9,15 @@
 //   brdf_objective_bwd        the gradients of the four predictions for five upstream gradients read on the device
 //   brdf_objective            forward + autograd node (five differentiable scalars)
 //   batch_ranking_loss(_fwd/_bwd)   wrapperIIW.py:88-109 with models.BatchRankingLoss, the whole batch in one call
-#include <dlfcn.h>
-
-#include <cstdlib>
-#include <string>
-#include <tuple>
-
-#include <ATen/ATen.h>
-#include <ATen/core/dispatch/Dispatcher.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/csrc/autograd/custom_function.h>
-#include <torch/library.h>
-
-#include "../../include/sgrender.h"
+#include "sgr_torch_common.hpp"
 
 namespace {
 
-using at::Tensor;
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-using OT = c10::optional<Tensor>;
+using namespace sgr_host;
+using OT = OptTensor;
 using W4 = at::ArrayRef<double>;
-using T2 = std::tuple<Tensor, Tensor>;
-using T3 = std::tuple<Tensor, Tensor, Tensor>;
-using T4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
-using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
-
-#define BO_API_LIST(X)                                                                                                                              \
-  X(sgr_abi_version) X(sgr_last_error) X(sgr_brdf_objective_workspace_floats) X(sgr_brdf_objective_fwd) X(sgr_brdf_objective_finalize) X(sgr_brdf_objective_bwd) \
-  X(sgr_ranking_loss_workspace_floats) X(sgr_ranking_loss_fwd) X(sgr_ranking_loss_bwd)
-
-struct Api {
-#define BO_DECL(name) decltype(&::name) name = nullptr;
-  BO_API_LIST(BO_DECL)
-#undef BO_DECL
-  std::string path;
-};
-
-void anchor() {}
-
-const Api& api() {
-  static const Api a = [] {
-    Api r;
-    const char* env = std::getenv("SGR_LIB");
-    if (env && env[0]) {
-      r.path = env;
-    } else {
-      Dl_info info{};
-      TORCH_CHECK(dladdr(reinterpret_cast<void*>(&anchor), &info) && info.dli_fname, "sgrender: cannot locate the torch extension on disk");
-      std::string self = info.dli_fname;
-      const auto slash = self.find_last_of('/');
-      r.path = (slash == std::string::npos ? std::string(".") : self.substr(0, slash)) + "/libsgrender.so";
-    }
-    void* h = dlopen(r.path.c_str(), RTLD_NOW | RTLD_LOCAL);
-    TORCH_CHECK(h, "sgrender: cannot load ", r.path, " (", dlerror(), "): the HIP library has not been built.  This package has no CPU / PyTorch fallback.");
-#define BO_LOAD(name)                                                      \
-  r.name = reinterpret_cast<decltype(r.name)>(dlsym(h, #name));            \
-  TORCH_CHECK(r.name, "sgrender: ", r.path, " does not export " #name "; stale build?");
-    BO_API_LIST(BO_LOAD)
-#undef BO_LOAD
-    TORCH_CHECK(r.sgr_abi_version() == SGR_ABI_VERSION, "sgrender: ", r.path, " has ABI version ", r.sgr_abi_version(), ", this extension needs ", SGR_ABI_VERSION);
-    return r;
-  }();
-  return a;
-}
-
-void ok(int rc, const char* what) {
-  if (rc != 0) {
-    const char* msg = api().sgr_last_error();
-    TORCH_CHECK(false, "sgrender: ", what, " failed (code ", rc, "): ", msg ? msg : "");
-  }
-}
-
-constexpr const char* kNoCpu =
-    "sgrender: this layer runs only on HIP device tensors (MI355X); there is no CPU path. Move the inputs to the GPU (the reference's "
-    "isCuda=True mode).";
-
-void* stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStream(dev.index()).stream(); }
-
-template <typename Sig>
-auto find_op(const char* name) {
-  return c10::Dispatcher::singleton().findSchemaOrThrow(name, "").typed<Sig>();
-}
 
 bool has(const OT& t) { return t.has_value() && t->defined(); }
-const float* rp(const Tensor& t) { return t.defined() ? t.const_data_ptr<float>() : nullptr; }
-float* wp(Tensor& t) { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; }
 
 // ---- the objective: argument checks shared by the device and the Meta kernels -----------------------------------------------------------
 struct Planes {
@@ -421,8 +343,6 @@ T2 ranking_autograd(RANK_ARGS, double tau) {
   return {o[0], o[1]};
 }
 
-void no_cpu_path(const c10::OperatorHandle&, torch::jit::Stack*) { TORCH_CHECK(false, kNoCpu); }
-
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(sgrender, m) {
@@ -458,7 +378,6 @@ TORCH_LIBRARY_IMPL(sgrender, Autograd, m) {
   m.impl("batch_ranking_loss", &ranking_autograd);
 }
 TORCH_LIBRARY_IMPL(sgrender, CPU, m) {
-  for (const char* name : {"brdf_objective_fwd", "brdf_objective_finalize", "brdf_objective_bwd", "brdf_objective", "batch_ranking_loss_fwd", "batch_ranking_loss_bwd",
-                           "batch_ranking_loss"})
-    m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_path>());
+  register_no_cpu(m, {"brdf_objective_fwd", "brdf_objective_finalize", "brdf_objective_bwd", "brdf_objective", "batch_ranking_loss_fwd", "batch_ranking_loss_bwd",
+                      "batch_ranking_loss"});
 }

@@ -323,73 +323,47 @@ def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, la
         seg = F.adaptive_avg_pool2d(seg, (R, C))
     eh, ew, fov, F0, cam = impl.envHeight, impl.envWidth, impl.fov_deg, float(impl.F0), impl._cam
     handoff = _ops.tan_handoff() and not heads
-    if brdf_grads:
-        return _light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, envmapsBatch, envmapsIndBatch, eh, ew, fov, F0, cam,
-                                     float(renderWeight), float(reconWeight), float(offset), heads, handoff, group,
-                                     (albedoPred, normalPred, roughPred, imBatch, segBRDFBatch, envmapsBatch, envmapsIndBatch))
-    # differentiable w.r.t. the SG parameters only -- on BOTH routes (the one-rank operator raised, the sharded route ran its
-    # stage operators under no_grad and silently returned no gradient for a BRDF map that still carried one)
-    if torch.is_grad_enabled():
-        for name, t in (("albedoPred", albedoPred), ("normalPred", normalPred), ("roughPred", roughPred), ("imBatch", imBatch), ("segBRDFBatch", segBRDFBatch),
-                        ("envmapsBatch", envmapsBatch), ("envmapsIndBatch", envmapsIndBatch)):
-            if t.requires_grad:
-                raise RuntimeError(f"sgrender: light_objective is differentiable with respect to the SG parameters only; {name} requires grad -- "
-                                   "detach it (wrapperBRDFLight.py:194 detaches albedoPred; the other maps come from frozen networks), or use "
-                                   "forwardSG + render_loss + recon_loss for gradients with respect to the BRDF maps")
+    # What may require grad is settled before any launch or collective, on BOTH routes (the one-rank operator raised, the
+    # sharded route ran its stage operators under no_grad and silently returned no gradient for a BRDF map that still carried one)
+    grad = torch.is_grad_enabled()
+    images = (("imBatch", imBatch), ("segBRDFBatch", segBRDFBatch), ("envmapsBatch", envmapsBatch), ("envmapsIndBatch", envmapsIndBatch))
+    maps = (("albedoPred", albedoPred), ("normalPred", normalPred), ("roughPred", roughPred))
+    for name, t in ((images if brdf_grads else maps + images) if grad else ()):
+        if not t.requires_grad:
+            continue
+        if brdf_grads:
+            raise RuntimeError(f"sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only; {name} requires grad -- "
+                               "detach it")
+        raise RuntimeError(f"sgrender: light_objective is differentiable with respect to the SG parameters only; {name} requires grad -- "
+                           "detach it (wrapperBRDFLight.py:194 detaches albedoPred; the other maps come from frozen networks), or use "
+                           "forwardSG + render_loss + recon_loss for gradients with respect to the BRDF maps")
+    live = [grad and brdf_grads and t.requires_grad for _, t in maps]
+    args = (a, n, r, axisPred, lambPred, weightPred, im, seg, envmapsBatch, envmapsIndBatch, eh, ew, fov, F0, cam, float(renderWeight), float(reconWeight),
+            float(offset), heads, handoff)
     if not _sharded(group):
         # one operator: forward statistics pass -> render loss -> [render-loss backward -> the objective's backward pass, which also
         # yields the reconstruction loss value and the scalar tail]; under torch.no_grad() / without a grad-requiring SG input the
-        # bracketed half shrinks to a loss-only pass (no gradient kernels are launched)
-        return tuple(_sg.light_objective(a, n, r, axisPred, lambPred, weightPred, im, seg, envmapsBatch, envmapsIndBatch, eh, ew, fov, F0, cam,
-                                         float(renderWeight), float(reconWeight), float(offset), heads, handoff))
-    # batch sharded over ranks: three stage operators with the two collectives between them
-    need = torch.is_grad_enabled() and (axisPred.requires_grad or lambPred.requires_grad or weightPred.requires_grad)
-    with torch.no_grad():
-        diffuse, spec, mask, coef, im_s, seg_s, rendered, coef_ds, sums, ws, lam_t, w_t = _sg.light_objective_stage1(
-            a, n, r, axisPred, lambPred, weightPred, im, seg, envmapsBatch, envmapsIndBatch, eh, ew, fov, F0, cam, heads, handoff and need)
-        _allreduce_sum_(sums, group)      # [num_r, den_r, 0, den_e]: one all-reduce before the backward pass
-        render_err, g_axis, g_lamb, g_weight, parts_b = _sg.light_objective_stage2(
-            a, n, r, axisPred, lambPred, weightPred, envmapsBatch, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
-            eh, ew, fov, F0, cam, float(renderWeight), float(reconWeight), float(offset), heads, need)
-        num_e = parts_b[0:1]
-        _allreduce_sum_(num_e, group)     # the second and last collective: the reconstruction numerator
-        objective, recon_err = _sg.light_objective_stage3(render_err, num_e, sums, float(renderWeight), float(reconWeight), eh, ew)
-    if need:      # every rank holds the gradient of the GLOBAL objective w.r.t. ITS shard (see combine_loss_parts)
-        applied = torch.ones(2, device=objective.device, dtype=torch.float32)
-        objective = _sg.attach_grads(objective, axisPred, lambPred, weightPred, g_axis, g_lamb, g_weight, applied)
-    return objective, render_err, recon_err, rendered, coef
+        # bracketed half shrinks to a loss-only pass (no gradient kernels are launched).  brdf_grads: then the BRDF maps' backward; with no
+        # grad-requiring map it is sgrender::light_objective itself (same launches, same node)
+        return tuple((_sg.light_objective_brdf if brdf_grads else _sg.light_objective)(*args))
+    return _light_objective_sharded(*args, group, live)
 
 
-def _light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads,
-                          handoff, group, caller):
-    """:func:`light_objective` with ``brdf_grads=True`` on the fused routes: ``a, n, r`` are the (pre-pooled) maps, ``caller`` the
-    caller's own tensors for the checks."""
-    albedoPred, normalPred, roughPred, imBatch, segBRDFBatch, envmapsBatch, envmapsIndBatch = caller
-    grad = torch.is_grad_enabled()
-    if grad:      # before any launch or collective, on both routes
-        for name, t in (("imBatch", imBatch), ("segBRDFBatch", segBRDFBatch), ("envmapsBatch", envmapsBatch), ("envmapsIndBatch", envmapsIndBatch)):
-            if t.requires_grad:
-                raise RuntimeError(f"sgrender: light_objective differentiates w.r.t. the SG parameters and the BRDF maps only; {name} requires grad -- "
-                                   "detach it")
-    live = [grad and t.requires_grad for t in (albedoPred, normalPred, roughPred)]
-    if not _sharded(group):
-        # one operator: with no grad-requiring map it is sgrender::light_objective itself (same launches, same node)
-        return tuple(_sg.light_objective_brdf(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w,
-                                              offset, heads, handoff))
-    need_sg = grad and (axisPred.requires_grad or lambPred.requires_grad or weightPred.requires_grad)
-    need = need_sg or any(live)
+def _light_objective_sharded(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads,
+                             handoff, group, live):
+    """The fused objective with the batch sharded over ranks: three stage operators with the two collectives between them.
+    ``live``: which of the maps ``a, n, r`` want a gradient (all ``False`` on the default route)."""
+    need = any(live) or (torch.is_grad_enabled() and (axisPred.requires_grad or lambPred.requires_grad or weightPred.requires_grad))
     with torch.no_grad():
         diffuse, spec, mask, coef, im_s, seg_s, rendered, coef_ds, sums, ws, lam_t, w_t = _sg.light_objective_stage1(
             a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind, eh, ew, fov, F0, cam, heads, handoff and need)
         _allreduce_sum_(sums, group)      # [num_r, den_r, 0, den_e]: one all-reduce before the backward pass
+        stage1 = (a, n, r, axisPred, lambPred, weightPred, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
+                  eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads)
         if any(live):
-            render_err, g_axis, g_lamb, g_weight, g_alb, g_nrm, g_rgh, parts_b = _sg.light_objective_stage2_brdf(
-                a, n, r, axisPred, lambPred, weightPred, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
-                eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, live[0], live[1], live[2])
+            render_err, g_axis, g_lamb, g_weight, g_alb, g_nrm, g_rgh, parts_b = _sg.light_objective_stage2_brdf(*stage1, *live)
         else:
-            render_err, g_axis, g_lamb, g_weight, parts_b = _sg.light_objective_stage2(
-                a, n, r, axisPred, lambPred, weightPred, env_gt, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws, lam_t, w_t,
-                eh, ew, fov, F0, cam, ren_w, rec_w, offset, heads, need)
+            render_err, g_axis, g_lamb, g_weight, parts_b = _sg.light_objective_stage2(*stage1, need)
         num_e = parts_b[0:1]
         _allreduce_sum_(num_e, group)     # the second and last collective: the reconstruction numerator
         objective, recon_err = _sg.light_objective_stage3(render_err, num_e, sums, ren_w, rec_w, eh, ew)
