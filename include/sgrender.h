@@ -493,6 +493,26 @@ int sgr_ranking_loss_bwd(const float* g_eq, const float* g_darker, const float* 
                          const int* darker_num, float* g_albedo_pred, int B, int H, int W, int n_eq, int n_darker, float tau,
                          void* stream);
 
+/* ---- the cascade-1 BRDF encoder's input (wrapperBRDF.py:56-100 = wrapperBRDFLight.py:58-92,106-108, trainFineTune*_cascade1.py:368-374,
+ * testReal.py:439-449).  Contract: DESIGN.md section 8c.
+ *   out [bn,17,H,W] = cat( im, norm(resize(albedo)), resize(normal'), resize(rough'), norm(resize(depth)),
+ *                          resize(c_im c_d diffuse), resize(c_im c_s spec) )
+ *   im [bn,3,H,W]; albedo, normal [bn,3,h,w]; rough, depth [bn,1,h,w]; diffuse, spec [bn,3,R,C].  A source of H x W is taken as it is,
+ *   one smaller than H x W along an axis is resized with F.interpolate(., [H,W], mode='bilinear') (align_corners=False); any other
+ *   source size is refused (the reference would fail in its torch.cat).
+ *   remap      x' = 0.5 (x + 1) for normal and rough, applied before the resize; otherwise x' = x
+ *   regress    (c_d, c_s, c_im) = models.LSregressDiffSpec (models.py:23-84) against adaptive_avg_pool2d(im, (R,C)); otherwise all 1
+ *   normalize  norm(x) = x / max(mean over the resized map of image b, 1e-10) / 3.0; otherwise norm(x) = x
+ *   coef [bn,2] = (c_im c_d, c_im c_s).
+ * At most three launches on `stream`, nothing read back, bit-identical runs, image b independent of the rest of the batch. */
+
+/* Floats of workspace for sgr_brdf_input_fwd.  Pure host function. */
+int sgr_brdf_input_workspace_floats(int bn);
+
+int sgr_brdf_input_fwd(const float* im, const float* albedo, const float* normal, const float* rough, const float* depth,
+                       const float* diffuse, const float* spec, float* out, float* coef, float* workspace, int bn, int H, int W, int h,
+                       int w, int R, int C, int regress, int normalize, int remap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,8 @@ SIGNATURES = {
     "sgr_ranking_loss_workspace_floats": ([_I], c_int),
     "sgr_ranking_loss_fwd": ([_P] * 9 + [_I] * 5 + [_F, _P], c_int),
     "sgr_ranking_loss_bwd": ([_P] * 10 + [_I] * 5 + [_F, _P], c_int),
+    "sgr_brdf_input_workspace_floats": ([_I], c_int),
+    "sgr_brdf_input_fwd": ([_P] * 10 + [_I] * 10 + [_P], c_int),
 }
 
 _lib = None

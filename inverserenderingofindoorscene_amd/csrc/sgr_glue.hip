@@ -9,6 +9,7 @@
 // Streaming, HBM-bound, launch-latency-sized work: block-partial reductions folded in a fixed order (no atomics,
 // bit-reproducible), everything stays on the caller's stream.
 #include "sgr_launch.h"
+#include "sgr_regress.h"      // src_index
 
 namespace sgr {
 
@@ -97,14 +98,6 @@ __global__ __launch_bounds__(kGlueThreads) void mean_stage(const float* __restri
     ws[((size_t)b * kGlueSplit + blockIdx.x) * 2 + 0] = acc[0];
     ws[((size_t)b * kGlueSplit + blockIdx.x) * 2 + 1] = acc[1];
   }
-}
-// torch's upsample_bilinear2d source index (align_corners = False): max(scale * (dst + 0.5) - 0.5, 0)
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
-  const float r = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
-  i0 = min((int)r, in_size - 1);
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = r - (float)i0;
-  l0 = 1.0f - l1;
 }
 // one thread per output pixel: 11 channels, the per-image albedo / depth scales applied per tap (the reference normalises
 // first, then interpolates); also writes the normalised albedo / depth maps the wrapper returns (threads with oy<h, ox<w)

@@ -11,6 +11,7 @@
 // `.item()` on pixelNum, wrapperBRDFLight.py:192, stays on the device).
 #include "sgr_launch.h"
 #include "sgr_recon_fold.h"
+#include "sgr_regress.h"      // diffspec_coefs, unit_coef
 
 namespace sgr {
 
@@ -102,21 +103,6 @@ __device__ __forceinline__ void fold_a(const float* __restrict__ wsA, int b, dou
 #pragma unroll
     for (int i = 0; i < 6; ++i) out[i] += __shfl_xor(out[i], off, 64);
   }
-}
-
-// (c_d, c_s) of models.py:44-63 from the five masked sums
-__device__ __forceinline__ void diffspec_coefs(const double (&s)[5], float n_elems, float& cd, float& cs) {
-  const float a11 = (float)s[0], a22 = (float)s[1], a12 = (float)s[2], b1 = (float)s[3], b2 = (float)s[4];
-  const float frac = a11 * a22 - a12 * a12;
-  const float c1 = (b1 * a22 - b2 * a12) / fmaxf(frac, 1e-2f);
-  const float c2 = (-b1 * a12 + a11 * b2) / fmaxf(frac, 1e-2f);
-  const float c3 = fminf(fmaxf(b1 / fmaxf(a11, 1e-5f), 0.001f), 1000.0f);
-  const bool two = (frac / n_elems) > 1e-2f;
-  cd = fminf(fmaxf(two ? c1 : c3, 0.0f), 1000.0f);
-  cs = fminf(fmaxf(two ? c2 : 0.0f, 0.0f), 1000.0f);
-}
-__device__ __forceinline__ float unit_coef(double num, double den) {   // models.py:13-14, 72-77
-  return fminf(fmaxf((float)num / fmaxf((float)den, 1e-5f), 0.001f), 1000.0f);
 }
 
 template <int POOL>
