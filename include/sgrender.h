@@ -513,6 +513,25 @@ int sgr_brdf_input_fwd(const float* im, const float* albedo, const float* normal
                        const float* diffuse, const float* spec, float* out, float* coef, float* workspace, int bn, int H, int W, int h,
                        int w, int R, int C, int regress, int normalize, int remap, void* stream);
 
+/* ---- BRDF-decoder output heads (models.decoder0.forward, models.py:189-203, and the wrappers' 0.5 (x + 1) on the albedo and depth
+ * decoders: wrapperBRDF.py, wrapperBRDFLight.py:112-115, wrapperNYU.py:89-92, wrapperIIW.py:83-86).  Contract: DESIGN.md section 8d.
+ * With s(x) = clamp(1.01 tanh(x), -1, 1):
+ *   albedo [bn,3,H,W] = s(x_c)                                   (mode 0)
+ *   normal [bn,3,H,W] = t_c / max(|t|, 1e-6),  t_c = s(x_c)      (mode 1)
+ *   rough  [bn,1,H,W] = (s(x_0) + s(x_1) + s(x_2)) / 3           (mode 2)
+ *   depth  [bn,1,H,W] = s((x_0 + x_1 + x_2) / 3)                 (mode 4)
+ * x_* are the dconvFinal outputs, [bn,3,H,W] each.  A NULL x leaves that decoder out: nothing is read or written for it.  `unit` != 0:
+ * albedo and depth in the wrappers' form, 0.5 (. + 1).  One launch on `stream`, no workspace, bit-identical runs. */
+int sgr_brdf_heads_fwd(const float* x_albedo, const float* x_normal, const float* x_rough, const float* x_depth, float* albedo,
+                       float* normal, float* rough, float* depth, int bn, int H, int W, int unit, void* stream);
+
+/* One launch: gx_* [bn,3,H,W] for the cotangents g_* (shaped like the outputs).  A NULL g is a zero cotangent; a NULL gx is not wanted
+ * (that decoder's tensors are not read).  The clamp passes the cotangent on the closed interval, like torch; below |t| = 1e-6 the norm
+ * path of the normal is blocked and the gradient is g / 1e-6 (the reference: NaN).  tanh is recomputed from x. */
+int sgr_brdf_heads_bwd(const float* x_albedo, const float* x_normal, const float* x_rough, const float* x_depth, const float* g_albedo,
+                       const float* g_normal, const float* g_rough, const float* g_depth, float* gx_albedo, float* gx_normal,
+                       float* gx_rough, float* gx_depth, int bn, int H, int W, int unit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,8 @@ SIGNATURES = {
     "sgr_ranking_loss_bwd": ([_P] * 10 + [_I] * 5 + [_F, _P], c_int),
     "sgr_brdf_input_workspace_floats": ([_I], c_int),
     "sgr_brdf_input_fwd": ([_P] * 10 + [_I] * 10 + [_P], c_int),
+    "sgr_brdf_heads_fwd": ([_P] * 8 + [_I] * 4 + [_P], c_int),
+    "sgr_brdf_heads_bwd": ([_P] * 12 + [_I] * 4 + [_P], c_int),
 }
 
 _lib = None

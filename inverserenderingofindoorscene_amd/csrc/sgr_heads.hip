@@ -7,23 +7,9 @@
 // lanes run along the pixels; ~14 separate elementwise kernels and their autograd graph in the reference.
 #include "sgr_launch.h"
 #include "sgr_math.h"
+#include "sgr_tanh.h"
 
 namespace sgr {
-
-// tanh to ~1 ulp: odd polynomial below 0.625 (no cancellation), 1 - 2/(e^{2|x|} + 1) above
-__device__ __forceinline__ float tanh_f(float x) {
-  const float ax = fabsf(x);
-  const float z = x * x;
-  float p = -5.70498872745e-3f;
-  p = fmaf(p, z, 2.06390887954e-2f);
-  p = fmaf(p, z, -5.37397155531e-2f);
-  p = fmaf(p, z, 1.33314422036e-1f);
-  p = fmaf(p, z, -3.33332819422e-1f);
-  const float small = fmaf(p * z, x, x);
-  const float e = fexp2(ax * 2.8853900817779268f);        // e^{2|x|}
-  const float big = copysignf(1.0f - 2.0f / (e + 1.0f), x);
-  return ax < 0.625f ? small : big;
-}
 
 // 0.5 * (1.01 t + 1) with torch's op-by-op rounding (the clamp kinks sit on these bits)
 __device__ __forceinline__ float unit_pre(float t) { return fmul_rn(0.5f, fadd_rn(fmul_rn(1.01f, t), 1.0f)); }
