@@ -532,6 +532,30 @@ int sgr_brdf_heads_bwd(const float* x_albedo, const float* x_normal, const float
                        const float* g_normal, const float* g_rough, const float* g_depth, float* gx_albedo, float* gx_normal,
                        float* gx_rough, float* gx_depth, int bn, int H, int W, int unit, void* stream);
 
+/* ---- CNN stage glue: GroupNorm + ReLU (+ skip concat + 2x bilinear upsample), the repeated stage of models.encoder0 / decoder0 /
+ * encoderLight / decoderLight around its convolution (models.py:122-127, 160-183, 262-267, 307-330).  Contract: DESIGN.md section 8e.
+ *   Cs == 0 (skip NULL):  out [B,C,H,W]        = relu(group_norm(x, G, weight, bias, eps))
+ *   Cs >= 1:              out [B,C+Cs,2H,2W]   = interpolate(cat([relu(group_norm(x)), skip], 1), scale_factor=2, mode='bilinear')
+ * x [B,C,H,W] and skip [B,Cs,H,W] are read through their element strides (x_strides / skip_strides: four long long each, host memory,
+ * read during the call), so channels-last tensors need no copy; out, the gradients and the cotangent are contiguous.  weight, bias [C].
+ * stats [B,G,4] = (mean, the mean's fp32 remainder, rstd, var) is written by the forward and is all the backward needs besides x.
+ * Moments are double-precision (sum, sum of squares) folds.  Forward: two launches; backward: at most three; no atomics, bit-identical
+ * runs, image b independent of the rest of the batch, the same bits for every layout of x and skip. */
+
+/* Floats of workspace (8-byte aligned, owned by the caller) for the forward (backward == 0) or the backward of the plain (upcat == 0) or
+ * the upsampling form.  Pure host function; 0 for sizes the entry points refuse. */
+long long sgr_gn_stage_workspace_floats(int B, int C, int G, int H, int W, int upcat, int backward);
+
+int sgr_gn_stage_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
+                     int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps,
+                     void* stream);
+
+/* g: the cotangent of out.  dx [B,C,H,W], dweight [C], dbias [C], dskip [B,Cs,H,W]: a NULL one is not wanted and costs nothing; x, weight,
+ * bias, stats and the workspace are needed only when dx, dweight or dbias is. */
+int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
+                     float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,9 @@ SIGNATURES = {
     "sgr_brdf_input_fwd": ([_P] * 10 + [_I] * 10 + [_P], c_int),
     "sgr_brdf_heads_fwd": ([_P] * 8 + [_I] * 4 + [_P], c_int),
     "sgr_brdf_heads_bwd": ([_P] * 12 + [_I] * 4 + [_P], c_int),
+    "sgr_gn_stage_workspace_floats": ([_I] * 7, c_longlong),
+    "sgr_gn_stage_fwd": ([_P] * 7 + [_I] * 6 + [_P, _P, _F, _P], c_int),
+    "sgr_gn_stage_bwd": ([_P] * 10 + [_I] * 6 + [_P, _P], c_int),
 }
 
 _lib = None

@@ -1,0 +1,523 @@
+// The repeated stage of the reference's four network classes (models.py:87-346) around its convolution, on gfx950:
+//   plain   y  [B,C,H,W]        = relu(group_norm(x, G, weight, bias, eps))                                  (encoder0 / encoderLight, :122-127)
+//   upcat   up [B,C+Cs,2H,2W]   = interpolate(cat([y, skip], 1), scale_factor=2, mode='bilinear')            (decoder0 / decoderLight, :160-183)
+// DESIGN.md section 8e states the contract; the per-element arithmetic is sgr_gn_stage.h.
+//
+// Forward, two launches: the moments of every (b, g) as double-precision (sum, sum of squares) partials, one per slice of the group, then
+// the apply kernel, which folds the partials of its group in a fixed order (every workgroup the same bits), writes the saved statistics
+// and streams the result: a thread produces two output rows of four columns from a 3 x 4 source neighbourhood, the skip channels through
+// the same code with the normalisation switched off.
+// Backward, three launches: pass 1 gathers the upsample's adjoint (4 x 4 output pixels per source pixel, no atomics), masks it with
+// y > 0 (y recomputed from x and the saved statistics), stores it (`dy`, C H W floats per image) and leaves double-precision partial sums
+// of dy and dy xhat per (b, c) slice; the skip channels leave pass 1 as dskip.  The fold makes the two per-(b, g) sums, dweight and
+// dbias, each by one wave in a fixed order.  Pass 2 writes dx.  Without a skip there is no adjoint and no `dy`: pass 2 masks the cotangent.
+//
+// x and skip are read through their strides (channels-last convolution outputs); every sum runs over logical indices, so the layout
+// changes no bit.  128-bit loads and stores where the layout and the alignment allow them, the same arithmetic element by element elsewhere.
+#include <stdint.h>
+
+#include "sgr_gn_stage.h"
+#include "sgr_launch.h"
+
+namespace sgr {
+
+constexpr int kGThreads = 256;
+constexpr int kGRounds = 8;            // positions per thread in the apply and backward kernels
+constexpr int kGSliceMin = 32768;      // elements of a group per moments workgroup, at least
+constexpr int kGSliceMax = 64;         // moments workgroups per (b, g), at most: one wave folds them
+
+struct GnStrides { long long b, c, h, w; };
+struct alignas(16) GVec4 { float v[4]; };
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+// the block's sums in thread 0, waves added in order
+__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 0) { lds[2 * wave] = a; lds[2 * wave + 1] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = lds[0]; b = lds[1];
+    for (int k = 1; k < nw; ++k) { a += lds[2 * k]; b += lds[2 * k + 1]; }
+  }
+}
+
+// slices of a group of n elements: a function of n alone, so that an image's sums do not depend on its batch
+static int gn_slices(long long n) {
+  long long s = (n + kGSliceMin - 1) / kGSliceMin;
+  return (int)(s < 1 ? 1 : s > kGSliceMax ? kGSliceMax : s);
+}
+static long long gn_slice_len(long long n) {
+  const long long per = (n + gn_slices(n) - 1) / gn_slices(n);
+  return (per + 4 * kGThreads - 1) / (4 * kGThreads) * (4 * kGThreads);
+}
+
+// partials[(b G + g) S + s] = (sum, sum of squares) over the logical elements [s L, (s+1) L) of the group; thread t takes the runs of four
+// at s L + 4 (k T + t), k = 0, 1, ..
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const float* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W,
+                                                               int HW, long long L) {
+  __shared__ double lds[2 * kGThreads / 64];
+  const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z, G = gridDim.y, S = gridDim.x;
+  const long long n = (long long)cpg * HW;
+  const long long e0 = (long long)s * L, e1 = e0 + L < n ? e0 + L : n;
+  const float* xb = x + (long long)b * xs.b + (long long)g * cpg * xs.c;
+  double sum = 0.0, sq = 0.0;
+  for (long long e = e0 + 4ll * threadIdx.x; e < e1; e += 4ll * blockDim.x) {
+    int c = (int)(e / HW), p = (int)(e - (long long)c * HW);
+    float v[4];
+    if (VEC) {
+      const GVec4 q = *reinterpret_cast<const GVec4*>(xb + (long long)c * xs.c + p);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = q.v[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        v[u] = 0.0f;
+        if (e + u < e1) {
+          const int h = p / W, w = p - h * W;
+          v[u] = xb[(long long)c * xs.c + (long long)h * xs.h + (long long)w * xs.w];
+        }
+        if (++p == HW) { p = 0; ++c; }
+      }
+    }
+    // a run past the end adds exact zeros: the bits do not depend on the path
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double d = (double)v[u];
+      sum += d;
+      sq = fma(d, d, sq);
+    }
+  }
+  block_sum2(sum, sq, lds);
+  if (threadIdx.x == 0) {
+    double* o = partials + 2 * (((long long)b * G + g) * S + s);
+    o[0] = sum;
+    o[1] = sq;
+  }
+}
+
+// the statistics of group (b, g) from its S <= 64 partials, by the first wave: lane s holds slice s, the lanes are added by wave_sum's tree
+__device__ __forceinline__ void gn_group_stat(const double* __restrict__ partials, int bg, int S, double n, float eps, float* sh) {
+  if (threadIdx.x < 64) {
+    double a = 0.0, q = 0.0;
+    if ((int)threadIdx.x < S) {
+      a = partials[2 * ((long long)bg * S + threadIdx.x)];
+      q = partials[2 * ((long long)bg * S + threadIdx.x) + 1];
+    }
+    a = wave_sum(a);
+    q = wave_sum(q);
+    if (threadIdx.x == 0) gn_finish(a, q, n, eps, sh[0], sh[1], sh[2], sh[3]);
+  }
+  __syncthreads();
+}
+
+// plain form: y = relu(gn(x)); a thread takes runs of four plane elements
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+                                                                   const float* __restrict__ bias, const double* __restrict__ partials,
+                                                                   float* __restrict__ stats, float* __restrict__ y, int C, int cpg, int W, int HW,
+                                                                   int S, float eps) {
+  __shared__ float sh[4];
+  const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
+  gn_group_stat(partials, b * G + g, S, (double)cpg * HW, eps, sh);
+  const float mh = sh[0], ml = sh[1], rstd = sh[2];
+  if (blockIdx.x == 0 && c == g * cpg && threadIdx.x == 0) {
+    float* st = stats + 4 * ((long long)b * G + g);
+    st[0] = mh; st[1] = ml; st[2] = rstd; st[3] = sh[3];
+  }
+  const float wc = weight[c], bc = bias[c];
+  const float* xp = x + (long long)b * xs.b + (long long)c * xs.c;
+  float* yp = y + ((long long)b * C + c) * HW;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds; ++r) {
+    const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
+    if (p >= HW) break;
+    GVec4 q;
+    if (VEC) {
+      q = *reinterpret_cast<const GVec4*>(xp + p);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int pu = p + u < HW ? p + u : HW - 1, h = pu / W, w = pu - h * W;
+        q.v[u] = xp[(long long)h * xs.h + (long long)w * xs.w];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q.v[u] = fmaxf(gn_pre(gn_xhat(q.v[u], mh, ml, rstd), wc, bc), 0.0f);
+    if (VEC) {
+      *reinterpret_cast<GVec4*>(yp + p) = q;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (p + u < HW) yp[p + u] = q.v[u];
+    }
+  }
+}
+
+// upcat form: channel ch < C is normalised x, ch >= C is skip as it is.  A thread at (i, jj) reads source rows i-1 .. i+1 x columns
+// 2jj-1 .. 2jj+2 (clamped) and writes output rows 2i, 2i+1 x columns 4jj .. 4jj+3.  VEC: 128-bit stores (W even, 16-byte aligned result).
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
+                                                                const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                const double* __restrict__ partials, float* __restrict__ stats,
+                                                                float* __restrict__ out, int C, int Cs, int cpg, int H, int W, int S, float eps) {
+  __shared__ float sh[4];
+  const int ch = blockIdx.y, b = blockIdx.z;
+  const bool norm = ch < C;      // uniform in the workgroup
+  float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
+  const float* src;
+  GnStrides st;
+  if (norm) {
+    const int G = C / cpg, g = ch / cpg;
+    gn_group_stat(partials, b * G + g, S, (double)cpg * H * W, eps, sh);
+    mh = sh[0]; ml = sh[1]; rstd = sh[2];
+    if (blockIdx.x == 0 && ch == g * cpg && threadIdx.x == 0) {
+      float* o = stats + 4 * ((long long)b * G + g);
+      o[0] = mh; o[1] = ml; o[2] = rstd; o[3] = sh[3];
+    }
+    wc = weight[ch]; bc = bias[ch];
+    src = x + (long long)b * xs.b + (long long)ch * xs.c;
+    st = xs;
+  } else {
+    src = skip + (long long)b * ss.b + (long long)(ch - C) * ss.c;
+    st = ss;
+  }
+  const int W2 = (W + 1) >> 1, OW = 2 * W;
+  float* op = out + ((long long)b * (C + Cs) + ch) * 4ll * H * W;
+  const unsigned sth = (unsigned)st.h, stw = (unsigned)st.w;      // in-plane offsets fit 31 bits (checked on the host)
+  const UpTaps taps = up_taps();
+  // the position (i, jj) of round 0 by one division, of the later rounds by steps of 256
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
+  int i = q0 / W2, jj = q0 - i * W2;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < H; ++r) {
+    const int c0 = 2 * jj;
+    const unsigned ro[3] = {(unsigned)(i > 0 ? i - 1 : 0) * sth, (unsigned)i * sth, (unsigned)(i + 1 < H ? i + 1 : H - 1) * sth};
+    const unsigned co[4] = {(unsigned)(c0 > 0 ? c0 - 1 : 0) * stw, (unsigned)c0 * stw, (unsigned)(c0 + 1 < W ? c0 + 1 : W - 1) * stw,
+                            (unsigned)(c0 + 2 < W ? c0 + 2 : W - 1) * stw};
+    float v[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float t = src[ro[a] + co[k]];
+        v[a][k] = norm ? fmaxf(gn_pre(gn_xhat(t, mh, ml, rstd), wc, bc), 0.0f) : t;
+      }
+    const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
+    GVec4 top, bot;
+    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top.v, bot.v);
+    float* o0 = op + (long long)(2 * i) * OW + 4 * jj;
+    if (VEC) {
+      *reinterpret_cast<GVec4*>(o0) = top;
+      *reinterpret_cast<GVec4*>(o0 + OW) = bot;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * jj + k < OW) { o0[k] = top.v[k]; o0[OW + k] = bot.v[k]; }
+    }
+    i += di;
+    jj += dj;
+    if (jj >= W2) { jj -= W2; ++i; }
+  }
+}
+
+// Backward pass 1 over the channels [c_begin, c_begin + gridDim.y) of cat([y, skip]).  UP: g is [B,C+Cs,2H,2W] and the adjoint is gathered;
+// otherwise g is [B,C,H,W] and taken as it is.  ch < C: dy = (y > 0) adjoint, stored to `dy` (if given) and summed; ch >= C: dskip = adjoint.
+template <bool VEC, bool UP>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __restrict__ g, const float* __restrict__ x, GnStrides xs,
+                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                 const float* __restrict__ stats, float* __restrict__ dy, float* __restrict__ dskip,
+                                                                 double* __restrict__ partials, int C, int Cs, int cpg, int H, int W, int c_begin) {
+  __shared__ double lds[2 * kGThreads / 64];
+  const int ch = c_begin + blockIdx.y, b = blockIdx.z, P = gridDim.x;
+  const bool norm = ch < C;
+  float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
+  const float* xp = nullptr;
+  if (norm) {
+    const float* st = stats + 4 * ((long long)b * (C / cpg) + ch / cpg);
+    mh = st[0]; ml = st[1]; rstd = st[2];
+    wc = weight[ch]; bc = bias[ch];
+    xp = x + (long long)b * xs.b + (long long)ch * xs.c;
+  }
+  const int W2 = (W + 1) >> 1, OW = UP ? 2 * W : W, OH = UP ? 2 * H : H;
+  const float* gp = g + ((long long)b * (C + Cs) + ch) * (long long)OH * OW;
+  float* dst = norm ? (dy ? dy + ((long long)b * C + ch) * H * W : nullptr) : dskip + ((long long)b * Cs + (ch - C)) * H * W;
+  double s1 = 0.0, s2 = 0.0;
+  const unsigned sh = (unsigned)xs.h, sw = (unsigned)xs.w;      // in-plane offsets fit 31 bits (checked on the host)
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];      // the adjoint weights at the low edge, inside and at the high edge of either axis
+  if (UP) { up_adj_sets(H, rl, rm, rh); up_adj_sets(W, cl, cm, chi); }
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
+  int i = q0 / W2, jj = q0 - i * W2;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < H; ++r) {
+    const int c0 = 2 * jj;
+    const bool two = c0 + 1 < W;
+    float a0, a1;
+    if (UP) {
+      float gv[4][6];
+      float wr[4], wa[4], wb[4];
+      up_adj_pick(rl, rm, rh, i, H, wr);
+      up_adj_pick(cl, cm, chi, c0, W, wa);
+      up_adj_pick(cl, cm, chi, c0 + 1, W, wb);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) wb[k] = two ? wb[k] : 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int orow = 2 * i - 1 + k;
+        const bool in = orow >= 0 && orow < OH;
+        const float* row = gp + (long long)(in ? orow : 0) * OW;
+        const int o = 4 * jj;
+        gv[k][0] = in && o > 0 ? row[o - 1] : 0.0f;
+        if (VEC) {
+          GVec4 t{{0.0f, 0.0f, 0.0f, 0.0f}};
+          if (in) t = *reinterpret_cast<const GVec4*>(row + o);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) gv[k][1 + u] = t.v[u];
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) gv[k][1 + u] = in && o + u < OW ? row[o + u] : 0.0f;
+        }
+        gv[k][5] = in && o + 4 < OW ? row[o + 4] : 0.0f;
+      }
+      up_adjoint(gv, wr, wa, wb, a0, a1);
+    } else {
+      a0 = gp[(long long)i * W + c0];
+      a1 = two ? gp[(long long)i * W + c0 + 1] : 0.0f;
+    }
+    if (norm) {
+      const float x0 = xp[(unsigned)i * sh + (unsigned)c0 * sw];
+      const float x1 = two ? xp[(unsigned)i * sh + (unsigned)(c0 + 1) * sw] : 0.0f;
+      const float h0 = gn_xhat(x0, mh, ml, rstd), h1 = gn_xhat(x1, mh, ml, rstd);
+      a0 = gn_pre(h0, wc, bc) > 0.0f ? a0 : 0.0f;
+      a1 = two && gn_pre(h1, wc, bc) > 0.0f ? a1 : 0.0f;
+      s1 += (double)a0;
+      s1 += (double)a1;
+      s2 = fma((double)a0, (double)h0, s2);
+      s2 = fma((double)a1, (double)h1, s2);
+    }
+    if (dst) {
+      dst[(long long)i * W + c0] = a0;
+      if (two) dst[(long long)i * W + c0 + 1] = a1;
+    }
+    i += di;
+    jj += dj;
+    if (jj >= W2) { jj -= W2; ++i; }
+  }
+  if (norm) {      // uniform in the workgroup
+    block_sum2(s1, s2, lds);
+    if (threadIdx.x == 0) {
+      double* o = partials + 2 * (((long long)b * C + ch) * P + blockIdx.x);
+      o[0] = s1;
+      o[1] = s2;
+    }
+  }
+}
+
+// One wave per job.  Jobs [0, B G): (c1, c2) of group (b, g) = sum over its channels and slices of w_c (s1, s2), over n.  Jobs
+// [B G, B G + C): dweight_c = sum over b and slices of s2, dbias_c of s1.  Lane l takes the entries l, l + 64, .. in order.
+__global__ __launch_bounds__(64) void gn_bwd_fold_kernel(const double* __restrict__ partials, const float* __restrict__ weight, float* __restrict__ coef,
+                                                         float* __restrict__ dweight, float* __restrict__ dbias, int B, int C, int cpg, int P,
+                                                         double n) {
+  const int G = C / cpg, job = blockIdx.x, lane = threadIdx.x;
+  double a = 0.0, q = 0.0;
+  if (job < B * G) {
+    const int b = job / G, g = job - b * G;
+    const double* base = partials + 2 * ((long long)b * C + (long long)g * cpg) * P;
+    for (int k = lane; k < cpg * P; k += 64) {
+      const double w = (double)weight[g * cpg + k / P];
+      a = fma(w, base[2 * k], a);
+      q = fma(w, base[2 * k + 1], q);
+    }
+    a = wave_sum(a);
+    q = wave_sum(q);
+    if (lane == 0 && coef) {
+      coef[2 * job] = (float)(a / n);
+      coef[2 * job + 1] = (float)(q / n);
+    }
+  } else {
+    const int c = job - B * G;
+    for (int k = lane; k < B * P; k += 64) {
+      const int b = k / P, s = k - b * P;
+      const double* e = partials + 2 * (((long long)b * C + c) * P + s);
+      a += e[0];
+      q += e[1];
+    }
+    a = wave_sum(a);
+    q = wave_sum(q);
+    if (lane == 0) {
+      if (dbias) dbias[c] = (float)a;
+      if (dweight) dweight[c] = (float)q;
+    }
+  }
+}
+
+// dx from dy (MASK = false: pass 1's masked adjoint) or from the cotangent itself (MASK = true: the plain form, masked here)
+template <bool VEC, bool MASK>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __restrict__ dy, const float* __restrict__ x, GnStrides xs,
+                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                 const float* __restrict__ stats, const float* __restrict__ coef,
+                                                                 float* __restrict__ dx, int C, int cpg, int W, int HW) {
+  const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
+  const float* st = stats + 4 * ((long long)b * G + g);
+  const float mh = st[0], ml = st[1], rstd = st[2], wc = weight[c], bc = bias[c];
+  const float c1 = coef[2 * (b * G + g)], c2 = coef[2 * (b * G + g) + 1];
+  const float* xp = x + (long long)b * xs.b + (long long)c * xs.c;
+  const float* dp = dy + ((long long)b * C + c) * HW;
+  float* op = dx + ((long long)b * C + c) * HW;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds; ++r) {
+    const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
+    if (p >= HW) break;
+    GVec4 xv, dv;
+    if (VEC) {
+      xv = *reinterpret_cast<const GVec4*>(xp + p);
+      dv = *reinterpret_cast<const GVec4*>(dp + p);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int pu = p + u < HW ? p + u : HW - 1, h = pu / W, w = pu - h * W;
+        xv.v[u] = xp[(long long)h * xs.h + (long long)w * xs.w];
+        dv.v[u] = dp[pu];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float xh = gn_xhat(xv.v[u], mh, ml, rstd);
+      const float d = !MASK || gn_pre(xh, wc, bc) > 0.0f ? dv.v[u] : 0.0f;
+      dv.v[u] = gn_dx(d, xh, wc, rstd, c1, c2);
+    }
+    if (VEC) {
+      *reinterpret_cast<GVec4*>(op + p) = dv;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (p + u < HW) op[p + u] = dv.v[u];
+    }
+  }
+}
+
+static bool g_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the planes of t are rows of W consecutive floats, H W % 4 == 0, and every plane starts on a 16-byte boundary
+static bool g_plane_vec(const float* t, const GnStrides& s, int H, int W) {
+  return s.w == 1 && s.h == W && (long long)H * W % 4 == 0 && s.c % 4 == 0 && s.b % 4 == 0 && g_al16(t);
+}
+// non-negative strides whose largest in-plane offset fits 31 bits: the kernels index a plane with 32-bit offsets
+static bool g_plane_fits(const long long* s, int H, int W) {
+  return s[2] >= 0 && s[3] >= 0 && (long long)(H - 1) * s[2] + (long long)(W - 1) * s[3] < (1ll << 31);
+}
+static int g_rounds_grid(long long items) { return (int)((items + (long long)kGThreads * kGRounds - 1) / ((long long)kGThreads * kGRounds)); }
+// slices of a plane in backward pass 1
+static int g_bwd_slices(int H, int W) { return g_rounds_grid((long long)H * ((W + 1) / 2)); }
+
+// floats of the group coefficients in the backward workspace, a multiple of four: what follows keeps the 16-byte alignment
+static long long g_coef_floats(int B, int G) { return (2ll * B * G + 3) / 4 * 4; }
+
+#define GN_CHECK_SIZES(who)                                                                              \
+  SGR_REQUIRE(B > 0 && C > 0 && G > 0 && H > 0 && W > 0 && Cs >= 0, who ": non-positive size");          \
+  SGR_REQUIRE(C % G == 0, who ": C is not a multiple of num_groups");                                    \
+  SGR_SUPPORTED(B <= 65535 && C + Cs <= 65535, who ": B or C + Cs > 65535");                             \
+  SGR_SUPPORTED((long long)H * W < (1ll << 26), who ": H * W out of range")
+
+}  // namespace sgr
+
+using namespace sgr;
+
+extern "C" long long sgr_gn_stage_workspace_floats(int B, int C, int G, int H, int W, int upcat, int backward) {
+  if (!(B > 0 && C > 0 && G > 0 && H > 0 && W > 0) || C % G != 0) return 0;
+  const long long HW = (long long)H * W;
+  if (!backward) return 4ll * B * G * gn_slices((long long)(C / G) * HW);
+  // partials (doubles), the group coefficients, then pass 1's masked adjoint where there is one
+  return 4ll * B * C * g_bwd_slices(H, W) + g_coef_floats(B, G) + (upcat ? (long long)B * C * HW : 0);
+}
+
+extern "C" int sgr_gn_stage_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
+                                int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps,
+                                void* stream) {
+  SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, "sgr_gn_stage_fwd: NULL tensor");
+  SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), "sgr_gn_stage_fwd: skip and its channel count do not agree");
+  GN_CHECK_SIZES("sgr_gn_stage_fwd");
+  SGR_REQUIRE(eps > 0.0f, "sgr_gn_stage_fwd: eps must be positive");
+  SGR_SUPPORTED(g_plane_fits(x_strides, H, W) && (!skip || g_plane_fits(skip_strides, H, W)), "sgr_gn_stage_fwd: negative or out-of-range plane strides");
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_fwd: the workspace must be 8-byte aligned");
+  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
+  const GnStrides ss = skip ? GnStrides{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]} : GnStrides{0, 0, 0, 0};
+  const int cpg = C / G, HW = H * W;
+  const long long n = (long long)cpg * HW;
+  const int S = gn_slices(n);
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const bool xvec = g_plane_vec(x, xs, H, W);
+  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
+  if (xvec)
+    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  else
+    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  if (!skip) {
+    const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C, B);
+    if (xvec && g_al16(out))
+      hipLaunchKernelGGL(gn_apply_plain_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+    else
+      hipLaunchKernelGGL(gn_apply_plain_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+  } else {
+    const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C + Cs, B);
+    if (W % 2 == 0 && g_al16(out))
+      hipLaunchKernelGGL(gn_apply_up_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+    else
+      hipLaunchKernelGGL(gn_apply_up_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_fwd");
+}
+
+extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
+                                float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
+                                void* stream) {
+  SGR_REQUIRE(g, "sgr_gn_stage_bwd: NULL cotangent");
+  SGR_REQUIRE(dx || dweight || dbias || dskip, "sgr_gn_stage_bwd: no gradient requested");
+  const bool side = dx || dweight || dbias;      // anything behind the normalisation
+  SGR_REQUIRE(!side || (x && weight && bias && stats && workspace && x_strides), "sgr_gn_stage_bwd: NULL tensor");
+  SGR_REQUIRE(!dskip || Cs > 0, "sgr_gn_stage_bwd: dskip requested without skip channels");
+  GN_CHECK_SIZES("sgr_gn_stage_bwd");
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_bwd: the workspace must be 8-byte aligned");
+  SGR_SUPPORTED(!side || g_plane_fits(x_strides, H, W), "sgr_gn_stage_bwd: negative or out-of-range plane strides");
+  const bool up = Cs > 0;
+  const int cpg = C / G, HW = H * W, P = g_bwd_slices(H, W);
+  const GnStrides xs = side ? GnStrides{x_strides[0], x_strides[1], x_strides[2], x_strides[3]} : GnStrides{0, 0, 0, 0};
+  hipStream_t st = (hipStream_t)stream;
+  double* partials = reinterpret_cast<double*>(workspace);
+  float* coef = side ? workspace + 4ll * B * C * P : nullptr;
+  float* dy = side && up && dx ? coef + g_coef_floats(B, G) : nullptr;
+  // pass 1: the channels somebody wants
+  const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
+  const dim3 grid1(P, c_end - c_begin, B);
+  if (up) {
+    if (W % 2 == 0 && g_al16(g))
+      hipLaunchKernelGGL((gn_bwd_pass1_kernel<true, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+    else
+      hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+  } else {
+    hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, false>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+  }
+  if (side) {
+    const int jobs = B * G + ((dweight || dbias) ? C : 0);
+    hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(jobs), dim3(64), 0, st, partials, weight, coef, dweight, dbias, B, C, cpg, P, (double)cpg * HW);
+  }
+  if (dx) {
+    const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
+    const float* d = up ? dy : g;
+    const bool vec = g_plane_vec(x, xs, H, W) && g_al16(d) && g_al16(dx);
+    if (up) {
+      if (vec) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+    } else {
+      if (vec) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, true>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, true>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+    }
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_bwd");
+}

@@ -1,11 +1,14 @@
-// Device arithmetic shared by the streaming operators (sgr_loss.hip, sgr_glue.hip, sgr_brdf_input.hip): the LSregress / LSregressDiffSpec
-// coefficients from their folded sums (models.py:7-21, 23-84) and torch's bilinear source index.  One definition each, so that the
-// operators that restate the same lines of the reference cannot drift apart.
+// Device arithmetic shared by the streaming operators (sgr_loss.hip, sgr_glue.hip, sgr_brdf_input.hip, sgr_gn_stage.hip): the LSregress /
+// LSregressDiffSpec coefficients from their folded sums (models.py:7-21, 23-84) and torch's bilinear source index.  One definition each,
+// so that the operators that restate the same lines of the reference cannot drift apart.  The source index also compiles for the host
+// (tests/host_emul, test infrastructure only).
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "sgr_math.h"
 
 namespace sgr {
+
+#if defined(__HIPCC__)
 
 // (c_d, c_s) of models.py:44-63 from the five masked sums
 __device__ __forceinline__ void diffspec_coefs(const double (&s)[5], float n_elems, float& cd, float& cs) {
@@ -22,10 +25,12 @@ __device__ __forceinline__ float unit_coef(double num, double den) {   // models
   return fminf(fmaxf((float)num / fmaxf((float)den, 1e-5f), 0.001f), 1000.0f);
 }
 
+#endif  // __HIPCC__
+
 // torch's upsample_bilinear2d source index (align_corners = False): max(scale * (dst + 0.5) - 0.5, 0)
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
+SGR_HD void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
   const float r = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
-  i0 = min((int)r, in_size - 1);
+  i0 = (int)r < in_size - 1 ? (int)r : in_size - 1;
   i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
   l1 = r - (float)i0;
   l0 = 1.0f - l1;

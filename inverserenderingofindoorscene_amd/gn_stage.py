@@ -1,0 +1,63 @@
+"""The repeated stage of the reference's network classes around its convolution, backed by libsgrender.so (csrc/sgr_gn_stage.hip).
+
+  ``group_norm_relu(x, weight, bias, num_groups, eps)``               ``F.relu(gn(x))`` of ``models.encoder0`` / ``encoderLight``
+                                                                      (models.py:122-127, 262-267 and the two ``preProcess`` pairs)
+  ``group_norm_relu_upcat(x, weight, bias, num_groups, skip, eps)``   ``F.interpolate(torch.cat([F.relu(dgnK(x)), skip], 1), scale_factor=2,
+                                                                      mode='bilinear')`` of ``models.decoder0`` / ``decoderLight``
+                                                                      (models.py:160-183, 307-330): what ``dconv{K+1}`` reads
+  ``GroupNormReLU(num_groups, num_channels, eps)``                    the module form; ``weight`` / ``bias`` load a checkpoint's ``gnK.*``
+
+Eager PyTorch spends four launches forward on a decoder stage (GroupNorm, ReLU, ``cat``, ``upsample_bilinear2d``) and keeps three maps for
+the backward; here it is two launches forward and three backward, and ``x`` with the per-group statistics is all that is kept.  DESIGN.md
+section 8e states the arithmetic."""
+from __future__ import annotations
+
+import torch
+
+from . import ops as _ops      # noqa: F401  (loads libsgrender_torch.so)
+
+__all__ = ["group_norm_relu", "group_norm_relu_upcat", "GroupNormReLU"]
+
+_sg = torch.ops.sgrender
+
+
+def group_norm_relu(x, weight, bias, num_groups: int, eps: float = 1e-5):
+    """``relu(F.group_norm(x, num_groups, weight, bias, eps))`` for fp32 ``x [B,C,H,W]`` on a HIP device, ``weight`` / ``bias [C]``,
+    ``C % num_groups == 0``.  ``x`` may be non-contiguous (a channels-last convolution output is read in place); the result is contiguous.
+    Differentiable with respect to ``x``, ``weight`` and ``bias``; a gradient is computed only for those that require it.  A CPU tensor
+    raises: there is no fallback."""
+    return _sg.gn_stage(x, weight, bias, None, int(num_groups), float(eps))[0]
+
+
+def group_norm_relu_upcat(x, weight, bias, num_groups: int, skip, eps: float = 1e-5):
+    """``F.interpolate(torch.cat([group_norm_relu(x, ...), skip], 1), scale_factor=2, mode='bilinear')``: ``[B, C + Cs, 2H, 2W]`` from
+    ``x [B,C,H,W]`` and ``skip [B,Cs,H,W]``, ``Cs >= 1``, both fp32 on a HIP device and possibly non-contiguous.  Differentiable with respect
+    to ``x``, ``weight``, ``bias`` and ``skip``.
+
+    A ``skip`` of another ``H, W`` raises: the reference resizes the normalised map first in that case (models.py:165-166 and its
+    siblings), and that branch stays the caller's -- ``group_norm_relu``, then torch's ``interpolate`` / ``cat``."""
+    if skip is None:
+        raise RuntimeError("sgrender: group_norm_relu_upcat: skip is None; group_norm_relu is the form without a skip")
+    return _sg.gn_stage(x, weight, bias, skip, int(num_groups), float(eps))[0]
+
+
+class GroupNormReLU(torch.nn.Module):
+    """``nn.GroupNorm(num_groups, num_channels, eps)`` followed by ReLU as one operator.  The parameters are named as ``nn.GroupNorm``'s, so
+    ``load_state_dict`` takes a reference checkpoint's ``gnK.weight`` / ``gnK.bias`` (``dgnK.*``) under the same prefix.
+    ``forward(x)`` is :func:`group_norm_relu`; ``forward(x, skip)`` is :func:`group_norm_relu_upcat`."""
+
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5):
+        super().__init__()
+        if num_channels % num_groups != 0:
+            raise ValueError(f"sgrender: GroupNormReLU: num_channels {num_channels} is not a multiple of num_groups {num_groups}")
+        self.num_groups, self.num_channels, self.eps = int(num_groups), int(num_channels), float(eps)
+        self.weight = torch.nn.Parameter(torch.ones(num_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(num_channels))
+
+    def forward(self, x, skip=None):
+        if skip is None:
+            return group_norm_relu(x, self.weight, self.bias, self.num_groups, self.eps)
+        return group_norm_relu_upcat(x, self.weight, self.bias, self.num_groups, skip, self.eps)
+
+    def extra_repr(self):
+        return f"{self.num_groups}, {self.num_channels}, eps={self.eps}"
