@@ -33,6 +33,13 @@ def test_pred_to_shading_vs_reference_fixture(sgr, tag):
     # batched tensor in, tensor out
     t = sgr.predToShading(torch.from_numpy(z[tag + "_pred"]).cuda().repeat(2, 1, 1, 1), envWidth=ew, envHeight=eh, SGNum=K)
     assert tuple(t.shape) == (2, 3, R, C) and rel_l2(t[1].cpu(), got) < 1e-6
+    # three DIFFERENT images (the cell grid mirrored left-right and up-down: the result is per cell, so it mirrors with it), each on its own:
+    # a wrong batch stride reads another image's lobes
+    p0 = torch.from_numpy(z[tag + "_pred"]).cuda()
+    t3 = sgr.predToShading(torch.cat([p0, p0.flip(3), p0.flip(2)]), envWidth=ew, envHeight=eh, SGNum=K)
+    assert tuple(t3.shape) == (3, 3, R, C) and not torch.equal(t3[1], t3[0]) and not torch.equal(t3[2], t3[0])
+    for b, want in enumerate((got, got[:, :, ::-1], got[:, ::-1, :])):
+        assert rel_l2(t3[b].cpu(), want.copy()) < 1e-6, b
 
 
 @pytest.mark.parametrize("tag", ["s1", "s2", "s3", "s4"])
