@@ -8,13 +8,12 @@
 // x_* are the dconvFinal outputs, [bn,3,H,W] each; a NULL x leaves that decoder out.  DESIGN.md section 8d states the contract.
 //
 // About 22 eager launches each way in the reference; here one launch each way.  A thread owns V consecutive pixels of one image across
-// the planes of every decoder present: V = 4 with 128-bit loads and stores when H W % 4 == 0 and every tensor is 16-byte aligned, the same
+// the planes of every decoder present (Vec<V> of sgr_reduce.h): V = 4 with 128-bit loads and stores when H W % 4 == 0 and every tensor is 16-byte aligned, the same
 // kernel element by element otherwise.  No reductions: no workspace, no atomics, bit-identical runs, image b independent of its batch.
 // The backward recomputes tanh from x.
-#include <stdint.h>
-
 #include "sgr_launch.h"
 #include "sgr_math.h"
+#include "sgr_reduce.h"       // Vec / ldv / stv, aligned16
 #include "sgr_tanh.h"
 
 namespace sgr {
@@ -25,14 +24,6 @@ enum { T_ALBEDO = 0, T_NORMAL, T_ROUGH, T_DEPTH };
 
 struct BrdfHeadsFwd { const float* x[4]; float* y[4]; };
 struct BrdfHeadsBwd { const float* x[4]; const float* g[4]; float* gx[4]; };
-
-template <int V> struct HVec;
-template <> struct HVec<1> { float v[1]; };
-template <> struct alignas(16) HVec<4> { float v[4]; };
-template <int V>
-__device__ __forceinline__ HVec<V> h_ld(const float* __restrict__ p, size_t i) { return *reinterpret_cast<const HVec<V>*>(p + i); }
-template <int V>
-__device__ __forceinline__ void h_st(float* __restrict__ p, size_t i, const HVec<V>& x) { *reinterpret_cast<HVec<V>*>(p + i) = x; }
 
 // s(x); the product is rounded on its own: the clamp's kinks sit on its bits
 __device__ __forceinline__ float h_act(float x) { return fminf(fmaxf(fmul_rn(1.01f, tanh_f(x)), -1.0f), 1.0f); }
@@ -55,41 +46,41 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_fwd_kernel(Brdf
     if (A.x[T_ALBEDO]) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        HVec<V> x = h_ld<V>(A.x[T_ALBEDO], i3 + (size_t)c * HW + o);
+        Vec<V> x = ldv<V>(A.x[T_ALBEDO], i3 + (size_t)c * HW + o);
 #pragma unroll
         for (int u = 0; u < V; ++u) {
           const float y = h_act(x.v[u]);
           x.v[u] = unit ? h_unit(y) : y;
         }
-        h_st<V>(A.y[T_ALBEDO], i3 + (size_t)c * HW + o, x);
+        stv<V>(A.y[T_ALBEDO], i3 + (size_t)c * HW + o, x);
       }
     }
     if (A.x[T_NORMAL]) {
-      HVec<V> x0 = h_ld<V>(A.x[T_NORMAL], i3 + o), x1 = h_ld<V>(A.x[T_NORMAL], i3 + HW + o), x2 = h_ld<V>(A.x[T_NORMAL], i3 + 2 * (size_t)HW + o);
+      Vec<V> x0 = ldv<V>(A.x[T_NORMAL], i3 + o), x1 = ldv<V>(A.x[T_NORMAL], i3 + HW + o), x2 = ldv<V>(A.x[T_NORMAL], i3 + 2 * (size_t)HW + o);
 #pragma unroll
       for (int u = 0; u < V; ++u) {
         const float t0 = h_act(x0.v[u]), t1 = h_act(x1.v[u]), t2 = h_act(x2.v[u]);
         const float n = fmaxf(h_norm(t0, t1, t2), 1e-6f);
         x0.v[u] = t0 / n; x1.v[u] = t1 / n; x2.v[u] = t2 / n;
       }
-      h_st<V>(A.y[T_NORMAL], i3 + o, x0); h_st<V>(A.y[T_NORMAL], i3 + HW + o, x1); h_st<V>(A.y[T_NORMAL], i3 + 2 * (size_t)HW + o, x2);
+      stv<V>(A.y[T_NORMAL], i3 + o, x0); stv<V>(A.y[T_NORMAL], i3 + HW + o, x1); stv<V>(A.y[T_NORMAL], i3 + 2 * (size_t)HW + o, x2);
     }
     if (A.x[T_ROUGH]) {
-      const HVec<V> x0 = h_ld<V>(A.x[T_ROUGH], i3 + o), x1 = h_ld<V>(A.x[T_ROUGH], i3 + HW + o), x2 = h_ld<V>(A.x[T_ROUGH], i3 + 2 * (size_t)HW + o);
-      HVec<V> y;
+      const Vec<V> x0 = ldv<V>(A.x[T_ROUGH], i3 + o), x1 = ldv<V>(A.x[T_ROUGH], i3 + HW + o), x2 = ldv<V>(A.x[T_ROUGH], i3 + 2 * (size_t)HW + o);
+      Vec<V> y;
 #pragma unroll
       for (int u = 0; u < V; ++u) y.v[u] = fadd_rn(fadd_rn(h_act(x0.v[u]), h_act(x1.v[u])), h_act(x2.v[u])) / 3.0f;
-      h_st<V>(A.y[T_ROUGH], i1 + o, y);
+      stv<V>(A.y[T_ROUGH], i1 + o, y);
     }
     if (A.x[T_DEPTH]) {
-      const HVec<V> x0 = h_ld<V>(A.x[T_DEPTH], i3 + o), x1 = h_ld<V>(A.x[T_DEPTH], i3 + HW + o), x2 = h_ld<V>(A.x[T_DEPTH], i3 + 2 * (size_t)HW + o);
-      HVec<V> y;
+      const Vec<V> x0 = ldv<V>(A.x[T_DEPTH], i3 + o), x1 = ldv<V>(A.x[T_DEPTH], i3 + HW + o), x2 = ldv<V>(A.x[T_DEPTH], i3 + 2 * (size_t)HW + o);
+      Vec<V> y;
 #pragma unroll
       for (int u = 0; u < V; ++u) {
         const float s = h_act(fadd_rn(fadd_rn(x0.v[u], x1.v[u]), x2.v[u]) / 3.0f);
         y.v[u] = unit ? h_unit(s) : s;
       }
-      h_st<V>(A.y[T_DEPTH], i1 + o, y);
+      stv<V>(A.y[T_DEPTH], i1 + o, y);
     }
   }
 }
@@ -99,7 +90,7 @@ template <int V>
 __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(BrdfHeadsBwd A, int HW, int unit) {
   const size_t i3 = (size_t)blockIdx.y * 3 * HW, i1 = (size_t)blockIdx.y * HW;
   const float us = unit ? 0.5f : 1.0f;
-  HVec<V> zero;
+  Vec<V> zero;
 #pragma unroll
   for (int u = 0; u < V; ++u) zero.v[u] = 0.0f;
   for (int o = (blockIdx.x * kHThreads + threadIdx.x) * V; o < HW; o += gridDim.x * kHThreads * V) {
@@ -107,9 +98,9 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(Brdf
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const size_t i = i3 + (size_t)c * HW + o;
-        HVec<V> r = zero;
+        Vec<V> r = zero;
         if (A.g[T_ALBEDO]) {
-          const HVec<V> x = h_ld<V>(A.x[T_ALBEDO], i), g = h_ld<V>(A.g[T_ALBEDO], i);
+          const Vec<V> x = ldv<V>(A.x[T_ALBEDO], i), g = ldv<V>(A.g[T_ALBEDO], i);
 #pragma unroll
           for (int u = 0; u < V; ++u) {
             float d;
@@ -117,14 +108,14 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(Brdf
             r.v[u] = us * g.v[u] * d;
           }
         }
-        h_st<V>(A.gx[T_ALBEDO], i, r);
+        stv<V>(A.gx[T_ALBEDO], i, r);
       }
     }
     if (A.gx[T_NORMAL]) {
-      HVec<V> r0 = zero, r1 = zero, r2 = zero;
+      Vec<V> r0 = zero, r1 = zero, r2 = zero;
       if (A.g[T_NORMAL]) {
-        const HVec<V> x0 = h_ld<V>(A.x[T_NORMAL], i3 + o), x1 = h_ld<V>(A.x[T_NORMAL], i3 + HW + o), x2 = h_ld<V>(A.x[T_NORMAL], i3 + 2 * (size_t)HW + o);
-        const HVec<V> g0 = h_ld<V>(A.g[T_NORMAL], i3 + o), g1 = h_ld<V>(A.g[T_NORMAL], i3 + HW + o), g2 = h_ld<V>(A.g[T_NORMAL], i3 + 2 * (size_t)HW + o);
+        const Vec<V> x0 = ldv<V>(A.x[T_NORMAL], i3 + o), x1 = ldv<V>(A.x[T_NORMAL], i3 + HW + o), x2 = ldv<V>(A.x[T_NORMAL], i3 + 2 * (size_t)HW + o);
+        const Vec<V> g0 = ldv<V>(A.g[T_NORMAL], i3 + o), g1 = ldv<V>(A.g[T_NORMAL], i3 + HW + o), g2 = ldv<V>(A.g[T_NORMAL], i3 + 2 * (size_t)HW + o);
 #pragma unroll
         for (int u = 0; u < V; ++u) {
           float d0, d1, d2;
@@ -138,13 +129,13 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(Brdf
           r2.v[u] = (g2.v[u] - t2 * dot) * inv * d2;
         }
       }
-      h_st<V>(A.gx[T_NORMAL], i3 + o, r0); h_st<V>(A.gx[T_NORMAL], i3 + HW + o, r1); h_st<V>(A.gx[T_NORMAL], i3 + 2 * (size_t)HW + o, r2);
+      stv<V>(A.gx[T_NORMAL], i3 + o, r0); stv<V>(A.gx[T_NORMAL], i3 + HW + o, r1); stv<V>(A.gx[T_NORMAL], i3 + 2 * (size_t)HW + o, r2);
     }
     if (A.gx[T_ROUGH]) {
-      HVec<V> r0 = zero, r1 = zero, r2 = zero;
+      Vec<V> r0 = zero, r1 = zero, r2 = zero;
       if (A.g[T_ROUGH]) {
-        const HVec<V> x0 = h_ld<V>(A.x[T_ROUGH], i3 + o), x1 = h_ld<V>(A.x[T_ROUGH], i3 + HW + o), x2 = h_ld<V>(A.x[T_ROUGH], i3 + 2 * (size_t)HW + o);
-        const HVec<V> g = h_ld<V>(A.g[T_ROUGH], i1 + o);
+        const Vec<V> x0 = ldv<V>(A.x[T_ROUGH], i3 + o), x1 = ldv<V>(A.x[T_ROUGH], i3 + HW + o), x2 = ldv<V>(A.x[T_ROUGH], i3 + 2 * (size_t)HW + o);
+        const Vec<V> g = ldv<V>(A.g[T_ROUGH], i1 + o);
 #pragma unroll
         for (int u = 0; u < V; ++u) {
           float d0, d1, d2;
@@ -153,13 +144,13 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(Brdf
           r0.v[u] = g3 * d0; r1.v[u] = g3 * d1; r2.v[u] = g3 * d2;
         }
       }
-      h_st<V>(A.gx[T_ROUGH], i3 + o, r0); h_st<V>(A.gx[T_ROUGH], i3 + HW + o, r1); h_st<V>(A.gx[T_ROUGH], i3 + 2 * (size_t)HW + o, r2);
+      stv<V>(A.gx[T_ROUGH], i3 + o, r0); stv<V>(A.gx[T_ROUGH], i3 + HW + o, r1); stv<V>(A.gx[T_ROUGH], i3 + 2 * (size_t)HW + o, r2);
     }
     if (A.gx[T_DEPTH]) {
-      HVec<V> r = zero;
+      Vec<V> r = zero;
       if (A.g[T_DEPTH]) {
-        const HVec<V> x0 = h_ld<V>(A.x[T_DEPTH], i3 + o), x1 = h_ld<V>(A.x[T_DEPTH], i3 + HW + o), x2 = h_ld<V>(A.x[T_DEPTH], i3 + 2 * (size_t)HW + o);
-        const HVec<V> g = h_ld<V>(A.g[T_DEPTH], i1 + o);
+        const Vec<V> x0 = ldv<V>(A.x[T_DEPTH], i3 + o), x1 = ldv<V>(A.x[T_DEPTH], i3 + HW + o), x2 = ldv<V>(A.x[T_DEPTH], i3 + 2 * (size_t)HW + o);
+        const Vec<V> g = ldv<V>(A.g[T_DEPTH], i1 + o);
 #pragma unroll
         for (int u = 0; u < V; ++u) {
           float d;
@@ -167,16 +158,11 @@ __global__ __launch_bounds__(kHThreads, kHWaves) void brdf_heads_bwd_kernel(Brdf
           r.v[u] = us * g.v[u] * d / 3.0f;
         }
       }
-      h_st<V>(A.gx[T_DEPTH], i3 + o, r); h_st<V>(A.gx[T_DEPTH], i3 + HW + o, r); h_st<V>(A.gx[T_DEPTH], i3 + 2 * (size_t)HW + o, r);
+      stv<V>(A.gx[T_DEPTH], i3 + o, r); stv<V>(A.gx[T_DEPTH], i3 + HW + o, r); stv<V>(A.gx[T_DEPTH], i3 + 2 * (size_t)HW + o, r);
     }
   }
 }
 
-static bool h_aligned(const void* const* ptrs, int n) {
-  for (int k = 0; k < n; ++k)
-    if ((uintptr_t)ptrs[k] & 15) return false;      // NULL counts as aligned
-  return true;
-}
 // workgroups per image: one round of V pixels per thread up to about 2048 in all, beyond which the threads stride (brdfin_pass_c's rule)
 static dim3 h_grid(int bn, int HW, int V) {
   const int want = (HW / V + kHThreads - 1) / kHThreads;
@@ -198,8 +184,7 @@ extern "C" int sgr_brdf_heads_fwd(const float* x_albedo, const float* x_normal, 
   SGR_SUPPORTED((long long)H * W < (1ll << 28), "sgr_brdf_heads_fwd: H * W out of range");
   const int HW = H * W;
   const BrdfHeadsFwd A{{x_albedo, x_normal, x_rough, x_depth}, {x_albedo ? albedo : nullptr, x_normal ? normal : nullptr, x_rough ? rough : nullptr, x_depth ? depth : nullptr}};
-  const void* ptrs[8] = {A.x[0], A.x[1], A.x[2], A.x[3], A.y[0], A.y[1], A.y[2], A.y[3]};
-  const bool vec = HW % 4 == 0 && h_aligned(ptrs, 8);
+  const bool vec = HW % 4 == 0 && aligned16({A.x[0], A.x[1], A.x[2], A.x[3], A.y[0], A.y[1], A.y[2], A.y[3]});      // a decoder left out: NULL, aligned
   if (vec)
     hipLaunchKernelGGL(brdf_heads_fwd_kernel<4>, h_grid(bn, HW, 4), dim3(kHThreads), 0, (hipStream_t)stream, A, HW, unit != 0);
   else
@@ -223,8 +208,7 @@ extern "C" int sgr_brdf_heads_bwd(const float* x_albedo, const float* x_normal, 
     if (!A.gx[k]) A.x[k] = A.g[k] = nullptr;      // neither read nor considered for the alignment
     if (!A.g[k]) A.x[k] = nullptr;
   }
-  const void* ptrs[12] = {A.x[0], A.x[1], A.x[2], A.x[3], A.g[0], A.g[1], A.g[2], A.g[3], A.gx[0], A.gx[1], A.gx[2], A.gx[3]};
-  const bool vec = HW % 4 == 0 && h_aligned(ptrs, 12);
+  const bool vec = HW % 4 == 0 && aligned16({A.x[0], A.x[1], A.x[2], A.x[3], A.g[0], A.g[1], A.g[2], A.g[3], A.gx[0], A.gx[1], A.gx[2], A.gx[3]});
   if (vec)
     hipLaunchKernelGGL(brdf_heads_bwd_kernel<4>, h_grid(bn, HW, 4), dim3(kHThreads), 0, (hipStream_t)stream, A, HW, unit != 0);
   else

@@ -7,9 +7,10 @@
 //   when it is H x W;  x' = 0.5 (x + 1) with `remap`;  norm(x) = x / max(mean_b(x), 1e-10) / 3.0 (the mean over the RESIZED map);
 //   (c_d, c_s, c_im) = models.LSregressDiffSpec against adaptive_avg_pool2d(im, (R,C)).  DESIGN.md section 8c states the contract.
 //
-// The reference spends about 30 eager launches on this; here it is at most three, in the scheme of sgr_brdf_loss.hip: grid = (kISplit, bn)
-// workgroups, fp32 per-thread partials, ONE partial set per workgroup in a workspace, folded in double in a fixed order by the consumer's
-// prologue -- no float atomics, no host synchronisation, bit-identical runs, image b's result independent of the batch around it.
+// The reference spends about 30 eager launches on this; here it is at most three, in the scheme of sgr_reduce.h: grid = (kISplit, bn)
+// workgroups, fp32 per-thread partials, ONE partial set per workgroup in a workspace (block_sum), folded in double in a fixed order by the
+// consumer's prologue (fold_lanes) -- no float atomics, no host synchronisation, bit-identical runs, image b's result independent of the
+// batch around it.
 //
 //   pass A   env grid: the pooled image formed on the fly from its window, the five masked regression sums;
 //            output grid: the sums of the resized albedo and depth, taps formed on the fly            (skipped: !regress && !normalize)
@@ -19,16 +20,14 @@
 //
 // Nothing is kept between the passes but the partials, so pass B forms the pooled image a second time (a re-read of `im` through the
 // cache) and pass C forms the albedo / depth taps a second time.
-#include <stdint.h>
-#include <initializer_list>
-
 #include "sgr_launch.h"
+#include "sgr_reduce.h"       // block_sum, fold_lanes, Vec / ldv / stv, aligned16
 #include "sgr_regress.h"
 
 namespace sgr {
 
-constexpr int kIThreads = 256;
-constexpr int kISplit = 64;          // workgroups per image of the two reducing passes = lanes of a wave (in_fold)
+constexpr int kIThreads = 256;        // four waves: what block_sum (sgr_reduce.h) is written for
+constexpr int kISplit = 64;          // workgroups per image of the two reducing passes = lanes of a wave (fold_lanes)
 constexpr int kIWaves = 4;           // waves per SIMD the passes are compiled for (<= 128 VGPRs), as sgr_brdf_loss.hip
 constexpr int kINA = 7;              // pass A's partials per workgroup
 constexpr int kINB = 2;              // pass B's
@@ -42,45 +41,9 @@ struct BrdfIn {
   int regress, normalize, remap;
 };
 
-template <int V> struct IVec;
-template <> struct IVec<1> { float v[1]; };
-template <> struct alignas(16) IVec<4> { float v[4]; };
-template <int V>
-__device__ __forceinline__ IVec<V> in_ld(const float* __restrict__ p, size_t i) { return *reinterpret_cast<const IVec<V>*>(p + i); }
-template <int V>
-__device__ __forceinline__ void in_st(float* __restrict__ p, size_t i, const IVec<V>& x) { *reinterpret_cast<IVec<V>*>(p + i) = x; }
-
-template <int N>
-__device__ __forceinline__ void in_block_reduce(float (&v)[N], float* lds /* [4*N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_down(v[i], off, 64);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[wave * N + i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (lds[i] + lds[N + i]) + (lds[2 * N + i] + lds[3 * N + i]);
-  }
-}
-
-// the kISplit partials of image b, component k: lane l takes partial l, xor butterfly in double (a fixed tree whose additions commute
-// pairwise: the same bits in every lane of every wave of every workgroup)
-__device__ __forceinline__ double in_fold(const float* __restrict__ ws, int b, int stride, int k) {
-  static_assert(kISplit == 64, "one partial per lane");
-  double x = (double)ws[((size_t)b * kISplit + (threadIdx.x & 63)) * stride + k];
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
 __device__ __forceinline__ void in_coefs(const float* __restrict__ wsA, int b, int n, float& cd, float& cs) {
-  const double s5[5] = {in_fold(wsA, b, kINA, S_DD), in_fold(wsA, b, kINA, S_SS), in_fold(wsA, b, kINA, S_DS), in_fold(wsA, b, kINA, S_DI),
-                        in_fold(wsA, b, kINA, S_SI)};
+  const double s5[5] = {fold_lanes<kISplit>(wsA, b, kINA, S_DD), fold_lanes<kISplit>(wsA, b, kINA, S_SS), fold_lanes<kISplit>(wsA, b, kINA, S_DS), fold_lanes<kISplit>(wsA, b, kINA, S_DI),
+                        fold_lanes<kISplit>(wsA, b, kINA, S_SI)};
   diffspec_coefs(s5, (float)n, cd, cs);
 }
 
@@ -117,7 +80,7 @@ template <int V>
 __device__ __forceinline__ void in_stream_sum(const float* __restrict__ p, int n, int t0, float& acc) {
   for (int i = t0 * 4; i < n; i += kISplit * kIThreads * 4) {
     if (V == 4) {
-      const IVec<4> x = in_ld<4>(p, i);
+      const Vec<4> x = ldv<4>(p, i);
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc += x.v[u];
     } else {
@@ -170,7 +133,7 @@ __global__ __launch_bounds__(kIThreads, kIWaves) void brdfin_pass_a(BrdfIn A, fl
       }
     }
   }
-  in_block_reduce<kINA>(acc, lds);
+  block_sum<kINA>(acc, lds);
   if (threadIdx.x == 0) {      // a workgroup that received no element writes zeros
 #pragma unroll
     for (int k = 0; k < kINA; ++k) wsA[((size_t)b * kISplit + blockIdx.x) * kINA + k] = acc[k];
@@ -194,7 +157,7 @@ __global__ __launch_bounds__(kIThreads, kIWaves) void brdfin_pass_b(BrdfIn A, co
     acc[0] = fmaf(rr, v, acc[0]);
     acc[1] = fmaf(rr, rr, acc[1]);
   }
-  in_block_reduce<kINB>(acc, lds);
+  block_sum<kINB>(acc, lds);
   if (threadIdx.x == 0) {
     wsB[((size_t)b * kISplit + blockIdx.x) * kINB + 0] = acc[0];
     wsB[((size_t)b * kISplit + blockIdx.x) * kINB + 1] = acc[1];
@@ -204,10 +167,10 @@ __global__ __launch_bounds__(kIThreads, kIWaves) void brdfin_pass_b(BrdfIn A, co
 // ---- pass C: the 17 planes --------------------------------------------------------------------------------------------------------------
 // V consecutive pixels of one row (W % V == 0) of one source plane -> V output values; `same`: the plane already is H x W
 template <int V, typename F>
-__device__ __forceinline__ IVec<V> in_fetch(const float* __restrict__ p, bool same, int o, const Taps (&t)[V], F f) {
-  IVec<V> x;
+__device__ __forceinline__ Vec<V> in_fetch(const float* __restrict__ p, bool same, int o, const Taps (&t)[V], F f) {
+  Vec<V> x;
   if (same) {
-    x = in_ld<V>(p, o);
+    x = ldv<V>(p, o);
 #pragma unroll
     for (int u = 0; u < V; ++u) x.v[u] = f(x.v[u]);
   } else {
@@ -225,11 +188,11 @@ __global__ __launch_bounds__(kIThreads, kIWaves) void brdfin_pass_c(BrdfIn A, co
   float cd = 1.0f, cs = 1.0f, cim = 1.0f, ma = 1.0f, md = 1.0f;
   if (A.regress) {
     in_coefs(wsA, b, 3 * RC, cd, cs);
-    cim = unit_coef(in_fold(wsB, b, kINB, 0), in_fold(wsB, b, kINB, 1));
+    cim = unit_coef(fold_lanes<kISplit>(wsB, b, kINB, 0), fold_lanes<kISplit>(wsB, b, kINB, 1));
   }
   if (A.normalize) {      // wrapperBRDF.py:84,89: the mean over the resized map
-    ma = fmaxf((float)(in_fold(wsA, b, kINA, S_ALB) / (double)(3 * (size_t)HW)), 1e-10f);
-    md = fmaxf((float)(in_fold(wsA, b, kINA, S_DEP) / (double)HW), 1e-10f);
+    ma = fmaxf((float)(fold_lanes<kISplit>(wsA, b, kINA, S_ALB) / (double)(3 * (size_t)HW)), 1e-10f);
+    md = fmaxf((float)(fold_lanes<kISplit>(wsA, b, kINA, S_DEP) / (double)HW), 1e-10f);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     coef[2 * b] = cim * cd;
@@ -255,39 +218,34 @@ __global__ __launch_bounds__(kIThreads, kIWaves) void brdfin_pass_c(BrdfIn A, co
       if (!sameE) te[u] = in_taps(oy, ox + u, A.R, A.C, ey, ex);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) in_st<V>(ob, (size_t)c * HW + o, in_ld<V>(im, (size_t)c * HW + o));
+    for (int c = 0; c < 3; ++c) stv<V>(ob, (size_t)c * HW + o, ldv<V>(im, (size_t)c * HW + o));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      IVec<V> x = in_fetch<V>(al + (size_t)c * hw, sameM, o, tm, AsIs{});
+      Vec<V> x = in_fetch<V>(al + (size_t)c * hw, sameM, o, tm, AsIs{});
       if (norm) {
 #pragma unroll
         for (int u = 0; u < V; ++u) x.v[u] = x.v[u] / ma / 3.0f;
       }
-      in_st<V>(ob, (size_t)(3 + c) * HW + o, x);
+      stv<V>(ob, (size_t)(3 + c) * HW + o, x);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) in_st<V>(ob, (size_t)(6 + c) * HW + o, in_fetch<V>(nr + (size_t)c * hw, sameM, o, tm, remap));
-    in_st<V>(ob, (size_t)9 * HW + o, in_fetch<V>(ro, sameM, o, tm, remap));
+    for (int c = 0; c < 3; ++c) stv<V>(ob, (size_t)(6 + c) * HW + o, in_fetch<V>(nr + (size_t)c * hw, sameM, o, tm, remap));
+    stv<V>(ob, (size_t)9 * HW + o, in_fetch<V>(ro, sameM, o, tm, remap));
     {
-      IVec<V> x = in_fetch<V>(dp, sameM, o, tm, AsIs{});
+      Vec<V> x = in_fetch<V>(dp, sameM, o, tm, AsIs{});
       if (norm) {
 #pragma unroll
         for (int u = 0; u < V; ++u) x.v[u] = x.v[u] / md / 3.0f;
       }
-      in_st<V>(ob, (size_t)10 * HW + o, x);
+      stv<V>(ob, (size_t)10 * HW + o, x);
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) in_st<V>(ob, (size_t)(11 + c) * HW + o, in_fetch<V>(df + (size_t)c * RC, sameE, o, te, Scaled{cd, cim}));
+    for (int c = 0; c < 3; ++c) stv<V>(ob, (size_t)(11 + c) * HW + o, in_fetch<V>(df + (size_t)c * RC, sameE, o, te, Scaled{cd, cim}));
 #pragma unroll
-    for (int c = 0; c < 3; ++c) in_st<V>(ob, (size_t)(14 + c) * HW + o, in_fetch<V>(sp + (size_t)c * RC, sameE, o, te, Scaled{cs, cim}));
+    for (int c = 0; c < 3; ++c) stv<V>(ob, (size_t)(14 + c) * HW + o, in_fetch<V>(sp + (size_t)c * RC, sameE, o, te, Scaled{cs, cim}));
   }
 }
 
-static bool in_aligned(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 15) return false;
-  return true;
-}
 // wrapperBRDF.py:56-63,73-76: a source of the output's size is taken as it is, one smaller along an axis is resized; anything else would
 // fail in the reference's torch.cat
 static bool in_size_legal(int h, int w, int H, int W) { return (h == H && w == W) || h < H || w < W; }
@@ -316,7 +274,7 @@ extern "C" int sgr_brdf_input_fwd(const float* im, const float* albedo, const fl
   const dim3 grid(kISplit, bn), block(kIThreads);
   const bool sameM = h == H && w == W, sameE = R == H && C == W;
   if (regress || normalize) {
-    if (sameM && (h * w) % 4 == 0 && in_aligned({albedo, depth}))
+    if (sameM && (h * w) % 4 == 0 && aligned16({albedo, depth}))
       hipLaunchKernelGGL(brdfin_pass_a<4>, grid, block, 0, st, A, wsA);
     else
       hipLaunchKernelGGL(brdfin_pass_a<1>, grid, block, 0, st, A, wsA);
@@ -324,7 +282,7 @@ extern "C" int sgr_brdf_input_fwd(const float* im, const float* albedo, const fl
   if (regress) hipLaunchKernelGGL(brdfin_pass_b, grid, block, 0, st, A, wsA, wsB);
   // 128-bit accesses: W % 4 == 0 (four pixels of one row; every plane of every image then keeps its tensor's alignment) and aligned
   // tensors -- the output and the image always, a source only where it is read as it is
-  const bool vec = W % 4 == 0 && in_aligned({out, im}) && (!sameM || in_aligned({albedo, normal, rough, depth})) && (!sameE || in_aligned({diffuse, spec}));
+  const bool vec = W % 4 == 0 && aligned16({out, im}) && (!sameM || aligned16({albedo, normal, rough, depth})) && (!sameE || aligned16({diffuse, spec}));
   const int V = vec ? 4 : 1;
   const int want = (H * W / V + kIThreads - 1) / kIThreads;      // workgroups per image: one round of V pixels per thread ...
   const int cap = 2048 / bn > kISplit ? 2048 / bn : kISplit;      // ... up to about 2048 in all, beyond which the threads stride

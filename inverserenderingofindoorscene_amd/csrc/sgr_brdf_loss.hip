@@ -4,10 +4,10 @@
 //   IIW ranking objective .... wrapperIIW.py:88-109 with models.BatchRankingLoss (models.py:526-563)
 //
 // The objective is a streaming reduction over up to 18 full-resolution planes (88 MB at 16 x 240 x 320), so unlike the render loss of
-// sgr_loss.hip it is bandwidth territory, not launch territory.  Same scheme otherwise: grid = (kBSplit, bn) workgroups, fp32 per-thread
-// partials, wave reduction by shuffles, cross-wave through LDS, ONE partial per workgroup written to a workspace; the next kernel's
-// prologue folds the partials it needs in double in a fixed order -- no float atomics, no host synchronisation (the reference's two
-// `.item()` on the mask sums, wrapperBRDF.py:118-119, stay on the device), two runs are bit-identical.
+// sgr_loss.hip it is bandwidth territory, not launch territory.  Same scheme otherwise, the one sgr_reduce.h defines: grid = (kBSplit, bn)
+// workgroups, fp32 per-thread partials, block_sum, ONE partial per workgroup written to a workspace; the next kernel's prologue folds the
+// partials it needs with fold_lanes -- no float atomics, no host synchronisation (the reference's two `.item()` on the mask sums,
+// wrapperBRDF.py:118-119, stay on the device), two runs are bit-identical.
 //
 //   pass A     every plane once: the two LSregress sum pairs, the three mask sums, the normal / rough / angle numerators
 //   pass B     folds the regression sums of its image, re-reads the albedo and depth planes: the two numerators that need a coefficient
@@ -18,16 +18,16 @@
 //
 // Absent terms (NULL prediction) are neither read nor written.  Planes are read as 128-bit vectors when H*W is a multiple of four
 // (every plane of every image then starts on a 16-byte boundary), element by element otherwise.
-#include <stdint.h>
-#include <initializer_list>
 #include <stdio.h>
 
 #include "sgr_launch.h"
+#include "sgr_reduce.h"       // block_sum, fold_lanes, Vec / ldv / stv, aligned16
+#include "sgr_regress.h"      // unit_coef
 
 namespace sgr {
 
-constexpr int kBThreads = 256;
-constexpr int kBSplit = 64;          // workgroups per image of every pass = lanes of a wave (fold64): 1024 workgroups at batch 16, below the ~2048 beyond
+constexpr int kBThreads = 256;        // four waves: what block_sum (sgr_reduce.h) is written for
+constexpr int kBSplit = 64;          // workgroups per image of every pass = lanes of a wave (fold_lanes): 1024 workgroups at batch 16, below the ~2048 beyond
                                      // which a grid should stride instead; measured at 16 x 480 x 640: pass A 4.6-6.4 TB/s, the backward 6.35
 constexpr int kBWaves = 4;           // waves per SIMD the streaming passes are compiled for (<= 128 VGPRs): four workgroups per CU, so the 1024
                                      // workgroups of batch 16 are ONE round on 256 CUs (at three per CU the second round ran a third full)
@@ -39,46 +39,6 @@ struct BrdfPlanes {
   const float *aP, *aG, *nP, *nG, *rP, *rG, *dP, *dG;      // predictions / ground truth; a NULL prediction = term absent
   const float *sB, *sA, *sD;                             // segBRDF, segAll, the depth mask (== sA unless the caller has a separate one)
 };
-
-template <int V> struct Vec;
-template <> struct Vec<1> { float v[1]; };
-template <> struct alignas(16) Vec<4> { float v[4]; };
-template <int V>
-__device__ __forceinline__ Vec<V> ldv(const float* __restrict__ p, size_t i) { return *reinterpret_cast<const Vec<V>*>(p + i); }
-template <int V>
-__device__ __forceinline__ void stv(float* __restrict__ p, size_t i, const Vec<V>& x) { *reinterpret_cast<Vec<V>*>(p + i) = x; }
-
-template <int N>
-__device__ __forceinline__ void brdf_block_reduce(float (&v)[N], float* lds /* [4*N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_down(v[i], off, 64);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[wave * N + i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (lds[i] + lds[N + i]) + (lds[2 * N + i] + lds[3 * N + i]);
-  }
-}
-
-// the kBSplit partials of image b, component k: lane l takes partial l, xor butterfly in double (a fixed tree whose additions commute
-// pairwise: the same bits in every lane of every wave of every workgroup)
-__device__ __forceinline__ double fold64(const float* __restrict__ ws, int b, int stride, int k) {
-  static_assert(kBSplit == 64, "one partial per lane");
-  double x = (double)ws[((size_t)b * kBSplit + (threadIdx.x & 63)) * stride + k];
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-__device__ __forceinline__ float brdf_unit_coef(double num, double den) {      // models.py:13-14
-  return fminf(fmaxf((float)num / fmaxf((float)den, 1e-5f), 0.001f), 1000.0f);
-}
 
 // ---- pass A -------------------------------------------------------------------------------------------------------------------------
 template <int V>
@@ -154,7 +114,7 @@ __global__ __launch_bounds__(kBThreads, kBWaves) void brdf_pass_a(BrdfPlanes P, 
       }
     }
   }
-  brdf_block_reduce<kNA>(acc, lds);
+  block_sum<kNA>(acc, lds);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kNA; ++k) wsA[((size_t)b * kBSplit + blockIdx.x) * kNA + k] = acc[k];
@@ -168,8 +128,8 @@ __global__ __launch_bounds__(kBThreads, kBWaves) void brdf_pass_b(BrdfPlanes P, 
   __shared__ float lds[4 * kNB];
   const int b = blockIdx.y;
   const bool hasA = P.aP, hasD = P.dP;
-  const float cA = hasA ? brdf_unit_coef(fold64(wsA, b, kNA, A_PG), fold64(wsA, b, kNA, A_PP)) : 0.0f;
-  const float cD = hasD ? brdf_unit_coef(fold64(wsA, b, kNA, D_PG), fold64(wsA, b, kNA, D_PP)) : 0.0f;
+  const float cA = hasA ? unit_coef(fold_lanes<kBSplit>(wsA, b, kNA, A_PG), fold_lanes<kBSplit>(wsA, b, kNA, A_PP)) : 0.0f;
+  const float cD = hasD ? unit_coef(fold_lanes<kBSplit>(wsA, b, kNA, D_PG), fold_lanes<kBSplit>(wsA, b, kNA, D_PP)) : 0.0f;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     coef[2 * b] = cA;
     coef[2 * b + 1] = cD;
@@ -200,7 +160,7 @@ __global__ __launch_bounds__(kBThreads, kBWaves) void brdf_pass_b(BrdfPlanes P, 
       }
     }
   }
-  brdf_block_reduce<kNB>(acc, lds);
+  block_sum<kNB>(acc, lds);
   if (threadIdx.x == 0) {
     wsB[((size_t)b * kBSplit + blockIdx.x) * kNB + 0] = acc[0];
     wsB[((size_t)b * kBSplit + blockIdx.x) * kNB + 1] = acc[1];
@@ -219,7 +179,7 @@ __device__ __forceinline__ void brdf_values(const float* parts, float wA, float 
 }
 
 // one workgroup: the eight batch totals of this rank's shard.  Thread t takes partials t, t + 256, ... of all eight components (every load
-// issued before the first use), adds them in double, then a shuffle tree per wave and the four waves in order: a fixed tree.
+// issued before the first use), adds them in double, then the tree of sgr_reduce.h's block_sum in double (the ladder per wave, the four waves as (w0 + w1) + (w2 + w3)).
 __global__ __launch_bounds__(kBThreads) void brdf_totals(const float* __restrict__ wsA, const float* __restrict__ wsB, int nparts, float* __restrict__ parts,
                                                          float* __restrict__ values /* nullable */, float wA, float wN, float wR, float wD) {
   __shared__ double lds[(kBThreads / 64) * 8];
@@ -231,6 +191,8 @@ __global__ __launch_bounds__(kBThreads) void brdf_totals(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 8; ++k) s[k] += (double)v[k];
   }
+  // wave_sum's ladder and block_sum's fold, in double.  Written out: through wave_sum(s) the kernel comes out with its instructions in
+  // another order and four s_waitcnt fewer -- the same bits, but not the listing that was measured.
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
 #pragma unroll
@@ -370,7 +332,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_fwd(const float* __restrict
     }
   }
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < 2; ++k) {      // wave_sum's ladder, written out: as a call the kernel's instructions come out in another order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
   }
@@ -463,12 +425,7 @@ static BrdfPlanes brdf_planes(const float* aP, const float* aG, const float* nP,
   return BrdfPlanes{aP, aG, nP, nG, rP, rG, dP, dG, sB, sA, sD ? sD : sA};
 }
 // 128-bit accesses need H*W % 4 == 0 (then every plane of every image keeps its tensor's alignment) and 16-byte aligned tensors
-static bool brdf_vec4(int HW, std::initializer_list<const void*> ptrs) {
-  if (HW % 4) return false;
-  for (const void* p : ptrs)
-    if ((uintptr_t)p & 15) return false;
-  return true;
-}
+static bool brdf_vec4(int HW, std::initializer_list<const void*> ptrs) { return HW % 4 == 0 && aligned16(ptrs); }
 #define BRDF_PLANE_PTRS(P) P.aP, P.aG, P.nP, P.nG, P.rP, P.rG, P.dP, P.dG, P.sB, P.sA, P.sD
 static thread_local char brdf_msg[160];
 #define BRDF_CHECK_PLANES(P, who)                                   \

@@ -6,32 +6,16 @@
 //                                 of albedo and depth, bilinear resize (F.interpolate, align_corners=False) of the five
 //                                 maps to 480x640 and their concatenation [im, albedo, (normal+1)/2, (rough+1)/2, depth]
 //
-// Streaming, HBM-bound, launch-latency-sized work: block-partial reductions folded in a fixed order (no atomics,
-// bit-reproducible), everything stays on the caller's stream.
+// Streaming, HBM-bound, launch-latency-sized work: block-partial reductions (block_sum of sgr_reduce.h) folded
+// in a fixed order (no atomics, bit-reproducible), everything stays on the caller's stream.
 #include "sgr_launch.h"
+#include "sgr_reduce.h"
 #include "sgr_regress.h"      // src_index
 
 namespace sgr {
 
-constexpr int kGlueThreads = 256;
+constexpr int kGlueThreads = 256;      // four waves: what block_sum is written for
 constexpr int kGlueSplit = 64;
-
-template <int N>
-__device__ __forceinline__ void glue_block_sum(float (&v)[N], float* lds /* [4*N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_down(v[i], off, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[wave * N + i] = v[i];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (lds[i] + lds[N + i]) + (lds[2 * N + i] + lds[3 * N + i]);
-  __syncthreads();
-}
 
 // ---- testReal.py:421-432 --------------------------------------------------------------------------------------------
 // stage 1: partial sums of (diffuseScaled, diffuse, specScaled, spec) and the partial max of albedo
@@ -47,9 +31,10 @@ __global__ __launch_bounds__(kGlueThreads) void scale_stage1(const float* __rest
   }
   float m = -INFINITY;
   for (long long i = (long long)blockIdx.x * kGlueThreads + threadIdx.x; i < n_alb; i += (long long)kGlueSplit * kGlueThreads) m = fmaxf(m, albedo[i]);
-  glue_block_sum<4>(acc, lds);
+  block_sum<4>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again, mx is another array): it keeps the listing equal to the profiled one; drop at the next re-measurement
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));      // wave_sum's ladder with fmaxf, written out: as a call the kernel's instructions come out in another order
   if ((threadIdx.x & 63) == 0) mx[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -93,7 +78,8 @@ __global__ __launch_bounds__(kGlueThreads) void mean_stage(const float* __restri
   const float* dp = depth + (size_t)b * hw;
   for (int i = blockIdx.x * kGlueThreads + threadIdx.x; i < 3 * hw; i += kGlueSplit * kGlueThreads) acc[0] += a[i];
   for (int i = blockIdx.x * kGlueThreads + threadIdx.x; i < hw; i += kGlueSplit * kGlueThreads) acc[1] += dp[i];
-  glue_block_sum<2>(acc, lds);
+  block_sum<2>(acc, lds);
+  __syncthreads();      // as in scale_stage1
   if (threadIdx.x == 0) {
     ws[((size_t)b * kGlueSplit + blockIdx.x) * 2 + 0] = acc[0];
     ws[((size_t)b * kGlueSplit + blockIdx.x) * 2 + 1] = acc[1];

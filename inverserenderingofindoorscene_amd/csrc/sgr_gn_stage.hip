@@ -14,10 +14,10 @@
 //
 // x and skip are read through their strides (channels-last convolution outputs); every sum runs over logical indices, so the layout
 // changes no bit.  128-bit loads and stores where the layout and the alignment allow them, the same arithmetic element by element elsewhere.
-#include <stdint.h>
-
+// The wave ladder of the sums (wave_sum), the 128-bit vector (Vec<4>) and its alignment test (aligned16) are sgr_reduce.h's.
 #include "sgr_gn_stage.h"
 #include "sgr_launch.h"
+#include "sgr_reduce.h"       // wave_sum, Vec<4>, aligned16
 
 namespace sgr {
 
@@ -27,14 +27,8 @@ constexpr int kGSliceMin = 32768;      // elements of a group per moments workgr
 constexpr int kGSliceMax = 64;         // moments workgroups per (b, g), at most: one wave folds them
 
 struct GnStrides { long long b, c, h, w; };
-struct alignas(16) GVec4 { float v[4]; };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-// the block's sums in thread 0, waves added in order
+// the block's sums in thread 0: wave_sum per wave, then the waves added in order (their number comes from blockDim: 64 or 256 threads)
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* lds) {
   a = wave_sum(a);
   b = wave_sum(b);
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const float* __re
     int c = (int)(e / HW), p = (int)(e - (long long)c * HW);
     float v[4];
     if (VEC) {
-      const GVec4 q = *reinterpret_cast<const GVec4*>(xb + (long long)c * xs.c + p);
+      const Vec<4> q = *reinterpret_cast<const Vec<4>*>(xb + (long long)c * xs.c + p);
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = q.v[u];
     } else {
@@ -138,9 +132,9 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* 
   for (int r = 0; r < kGRounds; ++r) {
     const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
     if (p >= HW) break;
-    GVec4 q;
+    Vec<4> q;
     if (VEC) {
-      q = *reinterpret_cast<const GVec4*>(xp + p);
+      q = *reinterpret_cast<const Vec<4>*>(xp + p);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* 
 #pragma unroll
     for (int u = 0; u < 4; ++u) q.v[u] = fmaxf(gn_pre(gn_xhat(q.v[u], mh, ml, rstd), wc, bc), 0.0f);
     if (VEC) {
-      *reinterpret_cast<GVec4*>(yp + p) = q;
+      *reinterpret_cast<Vec<4>*>(yp + p) = q;
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -210,12 +204,12 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __r
         v[a][k] = norm ? fmaxf(gn_pre(gn_xhat(t, mh, ml, rstd), wc, bc), 0.0f) : t;
       }
     const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
-    GVec4 top, bot;
+    Vec<4> top, bot;
     up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top.v, bot.v);
     float* o0 = op + (long long)(2 * i) * OW + 4 * jj;
     if (VEC) {
-      *reinterpret_cast<GVec4*>(o0) = top;
-      *reinterpret_cast<GVec4*>(o0 + OW) = bot;
+      *reinterpret_cast<Vec<4>*>(o0) = top;
+      *reinterpret_cast<Vec<4>*>(o0 + OW) = bot;
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -275,8 +269,8 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __
         const int o = 4 * jj;
         gv[k][0] = in && o > 0 ? row[o - 1] : 0.0f;
         if (VEC) {
-          GVec4 t{{0.0f, 0.0f, 0.0f, 0.0f}};
-          if (in) t = *reinterpret_cast<const GVec4*>(row + o);
+          Vec<4> t{{0.0f, 0.0f, 0.0f, 0.0f}};
+          if (in) t = *reinterpret_cast<const Vec<4>*>(row + o);
 #pragma unroll
           for (int u = 0; u < 4; ++u) gv[k][1 + u] = t.v[u];
         } else {
@@ -374,10 +368,10 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __
   for (int r = 0; r < kGRounds; ++r) {
     const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
     if (p >= HW) break;
-    GVec4 xv, dv;
+    Vec<4> xv, dv;
     if (VEC) {
-      xv = *reinterpret_cast<const GVec4*>(xp + p);
-      dv = *reinterpret_cast<const GVec4*>(dp + p);
+      xv = *reinterpret_cast<const Vec<4>*>(xp + p);
+      dv = *reinterpret_cast<const Vec<4>*>(dp + p);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -393,7 +387,7 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __
       dv.v[u] = gn_dx(d, xh, wc, rstd, c1, c2);
     }
     if (VEC) {
-      *reinterpret_cast<GVec4*>(op + p) = dv;
+      *reinterpret_cast<Vec<4>*>(op + p) = dv;
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -402,10 +396,9 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __
   }
 }
 
-static bool g_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // the planes of t are rows of W consecutive floats, H W % 4 == 0, and every plane starts on a 16-byte boundary
 static bool g_plane_vec(const float* t, const GnStrides& s, int H, int W) {
-  return s.w == 1 && s.h == W && (long long)H * W % 4 == 0 && s.c % 4 == 0 && s.b % 4 == 0 && g_al16(t);
+  return s.w == 1 && s.h == W && (long long)H * W % 4 == 0 && s.c % 4 == 0 && s.b % 4 == 0 && aligned16({t});
 }
 // non-negative strides whose largest in-plane offset fits 31 bits: the kernels index a plane with 32-bit offsets
 static bool g_plane_fits(const long long* s, int H, int W) {
@@ -460,13 +453,13 @@ extern "C" int sgr_gn_stage_fwd(const float* x, const float* weight, const float
     hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   if (!skip) {
     const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-    if (xvec && g_al16(out))
+    if (xvec && aligned16({out}))
       hipLaunchKernelGGL(gn_apply_plain_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
     else
       hipLaunchKernelGGL(gn_apply_plain_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
   } else {
     const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C + Cs, B);
-    if (W % 2 == 0 && g_al16(out))
+    if (W % 2 == 0 && aligned16({out}))
       hipLaunchKernelGGL(gn_apply_up_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
     else
       hipLaunchKernelGGL(gn_apply_up_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
@@ -496,7 +489,7 @@ extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* wei
   const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
   const dim3 grid1(P, c_end - c_begin, B);
   if (up) {
-    if (W % 2 == 0 && g_al16(g))
+    if (W % 2 == 0 && aligned16({g}))
       hipLaunchKernelGGL((gn_bwd_pass1_kernel<true, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
     else
       hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
@@ -510,7 +503,7 @@ extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* wei
   if (dx) {
     const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
     const float* d = up ? dy : g;
-    const bool vec = g_plane_vec(x, xs, H, W) && g_al16(d) && g_al16(dx);
+    const bool vec = g_plane_vec(x, xs, H, W) && aligned16({d, dx});
     if (up) {
       if (vec) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
       else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);

@@ -4,18 +4,19 @@
 //   render loss .............. wrapperBRDFLight.py:170-171,192,197-207
 //
 // These are HBM-bound streaming reductions over a few MB (launch-latency territory at the
-// reference's sizes), so the structure is: grid = (SPLIT, bn) blocks, fp32 per-thread partials,
-// wave reduction by DPP shuffles, cross-wave through LDS, one partial per block written to a
-// workspace; the NEXT kernel's prologue folds the SPLIT partials of its image (in a fixed order,
-// in double) -- no atomics, bit-reproducible, no host synchronisation (the reference's
-// `.item()` on pixelNum, wrapperBRDFLight.py:192, stays on the device).
+// reference's sizes), so the structure is the scheme of sgr_reduce.h: grid = (SPLIT, bn) blocks, fp32
+// per-thread partials, block_sum, one partial per block written to a workspace; the NEXT kernel's
+// prologue folds the SPLIT partials of its image (fold / fold_lanes: a fixed order, in double) -- no
+// atomics, bit-reproducible, no host synchronisation (the reference's `.item()` on pixelNum,
+// wrapperBRDFLight.py:192, stays on the device).
 #include "sgr_launch.h"
 #include "sgr_recon_fold.h"
+#include "sgr_reduce.h"       // block_sum, fold_lanes
 #include "sgr_regress.h"      // diffspec_coefs, unit_coef
 
 namespace sgr {
 
-constexpr int kLossThreads = 256;
+constexpr int kLossThreads = 256;     // four waves: what block_sum (sgr_reduce.h) is written for
 static_assert(kLossThreads == kRThreads, "the fold side job of stage A runs on a stage-A workgroup");
 constexpr int kSplit = 16;           // blocks per image (passes over data the previous pass left in cache; 32: no change in the loop)
 #ifndef SGR_LOSS_SPLIT_BC
@@ -35,27 +36,7 @@ constexpr int kStreamUnrollBC = SGR_LOSS_UNROLL_BC;      // the second / third p
                                                         // launches: 25.1-25.5 -> 23.2 us (profiles/r06k_*); requesting that round BEFORE the per-image folds as well: 24.1-24.2, not kept
 constexpr int kSplitA = 64;          // blocks per image of the FIRST pass (stage A / diffspec_partial_a): it reads the full-resolution
                                      // image and mask cold from HBM, and a quarter of the blocks left it latency-bound (16.7 us in the
-                                     // training loop for 32 MB); = lanes of a wave, see fold_a
-
-template <int N>
-__device__ __forceinline__ void block_reduce(float (&v)[N], float* lds /* [4*N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_down(v[i], off, 64);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[wave * N + i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (lds[i] + lds[N + i]) + (lds[2 * N + i] + lds[3 * N + i]);
-  }
-  __syncthreads();
-}
+                                     // training loop for 32 MB); = lanes of a wave, see fold_lanes
 
 // fold the kSplit partials of image b (N values each) in double, fixed order.  (Measured in round 3 on WARM buffers: 64 blocks per
 // image for all three passes are 2 us slower than 16 -- the second and third pass read what the first left in cache and are not
@@ -70,8 +51,7 @@ __device__ __forceinline__ void fold(const float* __restrict__ ws, int b, double
   }
 }
 
-// the second pass's partials of image b (2 values each): sequentially (kSplit of them), or -- 64 of them -- one per lane and an xor butterfly
-// in double like fold_a (same bits in every lane of every wave)
+// the second pass's partials of image b (2 values each): sequentially (kSplit of them), or -- 64 of them -- one per lane (fold_lanes)
 __device__ __forceinline__ void fold_bc(const float* __restrict__ wsB, int b, double (&out)[2]) {
   if constexpr (kSplitBC == kSplit) {
     out[0] = out[1] = 0.0;
@@ -80,28 +60,7 @@ __device__ __forceinline__ void fold_bc(const float* __restrict__ wsB, int b, do
       out[1] += (double)wsB[((size_t)b * kSplit + s) * 2 + 1];
     }
   } else {
-    const int lane = threadIdx.x & 63;
-    out[0] = (double)wsB[((size_t)b * kSplitBC + lane) * 2 + 0];
-    out[1] = (double)wsB[((size_t)b * kSplitBC + lane) * 2 + 1];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      out[0] += __shfl_xor(out[0], off, 64);
-      out[1] += __shfl_xor(out[1], off, 64);
-    }
-  }
-}
-
-// the kSplitA stage-A partials of image b: lane l of every wave takes partial l, then an xor butterfly in double -- a fixed tree
-// whose additions commute pairwise, so all lanes of all waves end with the same bits
-__device__ __forceinline__ void fold_a(const float* __restrict__ wsA, int b, double (&out)[6]) {
-  static_assert(kSplitA == 64, "one partial per lane");
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) out[i] = (double)wsA[((size_t)b * kSplitA + lane) * 6 + i];
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) out[i] += __shfl_xor(out[i], off, 64);
+    fold_lanes<64>(wsB, b, 2, 0, out);      // kSplitBC == 64 here (the static_assert above)
   }
 }
 
@@ -162,7 +121,8 @@ __global__ __launch_bounds__(kLossThreads) void loss_stage_a(const float* __rest
       }
     }
   }
-  block_reduce<6>(acc, lds);
+  block_sum<6>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again): it keeps the listing equal to the profiled one; drop at the next re-measurement
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) wsA[((size_t)b * kSplitA + blockIdx.x) * 6 + k] = acc[k];
@@ -176,7 +136,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_stage_b(const float* __rest
   __shared__ float lds[4 * 2];
   const int b = blockIdx.y;
   double sA[6];
-  fold_a(wsA, b, sA);
+  fold_lanes<kSplitA>(wsA, b, 6, 0, sA);      // one stage-A partial per lane
   const double s5[5] = {sA[0], sA[1], sA[2], sA[3], sA[4]};
   float cd, cs;
   diffspec_coefs(s5, (float)n, cd, cs);
@@ -198,7 +158,8 @@ __global__ __launch_bounds__(kLossThreads) void loss_stage_b(const float* __rest
       }
     }
   }
-  block_reduce<2>(acc, lds);
+  block_sum<2>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again): it keeps the listing equal to the profiled one; drop at the next re-measurement
   if (threadIdx.x == 0) {
     wsB[((size_t)b * kSplitBC + blockIdx.x) * 2 + 0] = acc[0];
     wsB[((size_t)b * kSplitBC + blockIdx.x) * 2 + 1] = acc[1];
@@ -214,7 +175,9 @@ __device__ __forceinline__ void finalize_pair(const float num, const float den_r
   scale[0] = 1.0f / den / divisor;
 }
 // sum of the pooled object mask over the shard (stage A's sixth partial of every workgroup), in double, thread t adding partials
-// t, t + 256, ... and a fixed LDS tree: the same value in whichever workgroup evaluates it
+// t, t + 256, ... and a fixed LDS tree: the same value in whichever workgroup evaluates it.  (The tree is block_sum_double's of
+// sgr_reduce.h for one value; written out here and in stage C's tail because the shared form swaps the operands of the tree's
+// additions in the listing -- the same bits, but not the same instructions.)
 __device__ __forceinline__ double shard_mask_total(const float* __restrict__ wsA, int nparts_a, double* lds /* [kLossThreads] */) {
   double den = 0.0;
   for (int i0 = threadIdx.x; i0 < nparts_a; i0 += kStreamUnroll * kLossThreads) {
@@ -257,7 +220,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_stage_c(const float* __rest
     gn = weight * (1.0f / den / divisor);      // finalize_pair's scale, loss_bwd's product
   }
   double sA[6], sB[2];
-  fold_a(wsA, b, sA);
+  fold_lanes<kSplitA>(wsA, b, 6, 0, sA);      // one stage-A partial per lane
   fold_bc(wsB, b, sB);
   const double s5[5] = {sA[0], sA[1], sA[2], sA[3], sA[4]};
   float cd, cs;
@@ -295,7 +258,8 @@ __global__ __launch_bounds__(kLossThreads) void loss_stage_c(const float* __rest
       }
     }
   }
-  block_reduce<1>(acc, lds);
+  block_sum<1>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again): it keeps the listing equal to the profiled one; drop at the next re-measurement
   // The batch totals [num, den_raw] of this rank's shard, by whichever workgroup arrives last (no fourth launch): every
   // workgroup publishes its partial at agent scope, then draws a ticket; the holder of the last ticket reads all partials
   // back -- in index order, in double, through a fixed LDS tree: the result does not depend on which workgroup that is.
@@ -383,7 +347,8 @@ __global__ __launch_bounds__(kLossThreads) void dot2_partial(const float* __rest
     acc[0] = fmaf(x, y, acc[0]);
     acc[1] = fmaf(x, x, acc[1]);
   }
-  block_reduce<2>(acc, lds);
+  block_sum<2>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again): it keeps the listing equal to the profiled one; drop at the next re-measurement
   if (threadIdx.x == 0) {
     ws[((size_t)b * kSplit + blockIdx.x) * 2 + 0] = acc[0];
     ws[((size_t)b * kSplit + blockIdx.x) * 2 + 1] = acc[1];
@@ -411,16 +376,17 @@ __global__ __launch_bounds__(kLossThreads) void diffspec_partial_a(const float* 
     acc[0] = fmaf(d, d, acc[0]); acc[1] = fmaf(s, s, acc[1]); acc[2] = fmaf(d, s, acc[2]);
     acc[3] = fmaf(d, vm, acc[3]); acc[4] = fmaf(s, vm, acc[4]);
   }
-  block_reduce<6>(acc, lds);
+  block_sum<6>(acc, lds);
+  __syncthreads();      // not needed for correctness (lds is not written again): it keeps the listing equal to the profiled one; drop at the next re-measurement
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) wsA[((size_t)b * kSplitA + blockIdx.x) * 6 + k] = acc[k];
   }
 }
 __global__ __launch_bounds__(64) void diffspec_finish(const float* __restrict__ wsA, const float* __restrict__ wsB, float* __restrict__ coef, int n) {
-  const int b = blockIdx.x;      // one wave per image (fold_a is lane-cooperative)
+  const int b = blockIdx.x;      // one wave per image (fold_lanes is lane-cooperative)
   double sA[6], sB[2];
-  fold_a(wsA, b, sA);
+  fold_lanes<kSplitA>(wsA, b, 6, 0, sA);      // one stage-A partial per lane
   fold_bc(wsB, b, sB);
   const double s5[5] = {sA[0], sA[1], sA[2], sA[3], sA[4]};
   float cd, cs;

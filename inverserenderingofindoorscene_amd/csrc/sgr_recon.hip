@@ -6,8 +6,8 @@
 // at a time; for each colour its 64 lanes read the pixel's J contiguous floats as coalesced float2 /
 // float4 rows (512 B per wave-instruction), reduce the per-pixel sums by DPP shuffles, and the
 // per-block partials go to a workspace that the next stage folds in double, in a fixed order
-// (no atomics, bit-reproducible, no host synchronisation -- the reference's `.item()` on pixelNum,
-// wrapperBRDFLight.py:179, stays on the device).
+// (sgr_recon_fold.h, through block_sum_double of sgr_reduce.h; no atomics, bit-reproducible, no host
+// synchronisation -- the reference's `.item()` on pixelNum, wrapperBRDFLight.py:179, stays on the device).
 //
 //   stage 0: mask_p = segSmall_p * envInd_b * [mean_{c,j} gt > 0.001]                 (:172-174)
 //            per image  <pred m, gt m>, <pred m, pred m>  -> coef_b (clamped, models.py:13-14),  sum_p mask_p
@@ -33,7 +33,8 @@ __device__ __forceinline__ float2 ld2(const float* p) {
 }
 constexpr int kPixPerBlock = 64;
 
-__device__ __forceinline__ float wave_sum(float v) {
+// xor butterfly, off = 32 .. 1: the wave's sum in EVERY lane (not sgr_reduce.h's wave_sum, a ladder that leaves it in lane 0)
+__device__ __forceinline__ float wave_allsum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(kRThreads) void recon_stage0(const float* __restric
         }
       }
     }
-    sg = wave_sum(sg); seg_ = wave_sum(seg_); see = wave_sum(see);
+    sg = wave_allsum(sg); seg_ = wave_allsum(seg_); see = wave_allsum(see);
     const float not_dark = (sg / (3.0f * (float)J)) > 0.001f ? 1.0f : 0.0f;
     const float m = seg_small[(size_t)b * RC + p] * ind * not_dark;
     if (lane == 0) mask[(size_t)b * RC + p] = m;
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(kRThreads) void recon_stage1(const float* __restric
     }
     acc = fmaf(m, s, acc);
   }
-  acc = wave_sum(acc);
+  acc = wave_allsum(acc);
   if (lane == 0) red[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) ws[(size_t)b * nblk + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);

@@ -1,28 +1,14 @@
 // Deterministic folds of the env-reconstruction partial sums (shared by sgr_recon.hip and the fused
 // objective, sgr_fused_recon.hip): double accumulation in a fixed order, no atomics, no host sync.
+// Thread t adds partials t, t + THREADS, ..., then the fixed LDS tree of sgr_reduce.h (block_sum_double).
 #pragma once
 #include "sgr_launch.h"
+#include "sgr_reduce.h"
+#include "sgr_regress.h"      // unit_coef
 
 namespace sgr {
 
 constexpr int kRThreads = 256;
-
-// deterministic block sum in double: thread t adds elements t, t+256, ...; fixed LDS tree afterwards
-template <int N>
-__device__ __forceinline__ void block_sum_double(double (&v)[N], double* lds /* [256*N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) lds[threadIdx.x * N + i] = v[i];
-  __syncthreads();
-  for (int s = kRThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int i = 0; i < N; ++i) lds[threadIdx.x * N + i] += lds[(threadIdx.x + s) * N + i];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = lds[i];
-}
 
 // fold stage-0 partials of image b: coef[b] (LSregress scale, models.py:7-21), den partial per image.  One workgroup of kRThreads.
 __device__ __forceinline__ void recon_fold0_image(const float* __restrict__ ws, float* __restrict__ coef, float* __restrict__ den_img, int nblk, int b,
@@ -40,9 +26,9 @@ __device__ __forceinline__ void recon_fold0_image(const float* __restrict__ ws, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[0] += (double)t[j][0]; v[1] += (double)t[j][1]; v[2] += (double)t[j][2]; }
   }
-  block_sum_double<3>(v, lds);
+  block_sum_double<kRThreads>(v, lds);
   if (threadIdx.x == 0) {
-    coef[b] = fminf(fmaxf((float)v[0] / fmaxf((float)v[1], 1e-5f), 0.001f), 1000.0f);
+    coef[b] = unit_coef(v[0], v[1]);
     den_img[b] = (float)v[2];
   }
 }
@@ -80,18 +66,9 @@ static __global__ __launch_bounds__(kFold1Threads) void recon_fold1(const float*
   }
   double v[2] = {((w[0] + w[1]) + (w[2] + w[3])) + ((w[4] + w[5]) + (w[6] + w[7])), 0.0};
   for (int i = threadIdx.x; i < bn; i += kFold1Threads) v[1] += (double)den_img[i];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) lds[threadIdx.x * 2 + i] = v[i];
-  __syncthreads();
-  for (int s = kFold1Threads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      lds[threadIdx.x * 2] += lds[(threadIdx.x + s) * 2];
-      lds[threadIdx.x * 2 + 1] += lds[(threadIdx.x + s) * 2 + 1];
-    }
-    __syncthreads();
-  }
+  block_sum_double<kFold1Threads>(v, lds);
   if (threadIdx.x == 0) {
-    const float num = (float)lds[0], den = (float)lds[1];
+    const float num = (float)v[0], den = (float)v[1];
     parts[0] = num;
     parts[1] = den;
     if (tail.objective) {
@@ -102,6 +79,5 @@ static __global__ __launch_bounds__(kFold1Threads) void recon_fold1(const float*
     }
   }
 }
-
 
 }  // namespace sgr

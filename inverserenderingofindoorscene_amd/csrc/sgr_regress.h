@@ -1,7 +1,7 @@
-// Device arithmetic shared by the streaming operators (sgr_loss.hip, sgr_glue.hip, sgr_brdf_input.hip, sgr_gn_stage.hip): the LSregress /
+// Device arithmetic shared by the streaming operators (sgr_loss.hip, sgr_brdf_loss.hip, sgr_recon_fold.h, sgr_glue.hip, sgr_brdf_input.hip, sgr_gn_stage.hip): the LSregress /
 // LSregressDiffSpec coefficients from their folded sums (models.py:7-21, 23-84) and torch's bilinear source index.  One definition each,
 // so that the operators that restate the same lines of the reference cannot drift apart.  The source index also compiles for the host
-// (tests/host_emul, test infrastructure only).
+// (tests/host_emul, test infrastructure only).  The reductions that produce the folded sums are sgr_reduce.h (device only).
 #pragma once
 
 #include "sgr_math.h"
