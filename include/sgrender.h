@@ -556,6 +556,25 @@ int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const 
                      float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
                      void* stream);
 
+/* ---- The same stage with the reference's resize-to-skip branch taken (models.py:165-166, 170-171, 175-176, 180-181, 185-186; decoderLight:
+ * 312-313 ... 332-333): y = relu(group_norm(x)) [B,C,H,W] is resized to Hs x Ws by interpolate(., [Hs, Ws], mode='bilinear') first.
+ *   Cs == 0 (skip NULL):  out [B,C,Hs,Ws]       = the resized map                                   (the final stage)
+ *   Cs >= 1:              out [B,C+Cs,2Hs,2Ws]  = interpolate(cat([resized, skip], 1), scale_factor=2, mode='bilinear'),  skip [B,Cs,Hs,Ws]
+ * Domain, per axis: H <= Hs <= 2H and W <= Ws <= 2W (equal sizes included); anything else is refused as "outside the resize domain".
+ * The index rule is torch's for a given output size: scale = (float)H / (float)Hs in fp32, s = max(scale (o + 0.5) - 0.5, 0); a resized
+ * value is rounded to fp32 before the 2x stage reads it.  Everything else -- strides, stats, workspace alignment, NULL gradients -- as
+ * sgr_gn_stage_*.  Forward: two launches; backward: at most four (three when Cs == 0); no atomics, bit-identical runs. */
+long long sgr_gn_resize_workspace_floats(int B, int C, int G, int H, int W, int Hs, int Ws, int upcat, int backward);
+
+int sgr_gn_resize_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
+                      int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides, const long long* skip_strides,
+                      float eps, void* stream);
+
+/* g: the cotangent of out.  dx [B,C,H,W], dweight [C], dbias [C], dskip [B,Cs,Hs,Ws]. */
+int sgr_gn_resize_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
+                      float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
+                      const long long* x_strides, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // Per-element arithmetic of the CNN stage glue (sgr_gn_stage.hip): GroupNorm + ReLU, the 2x bilinear upsample of models.py:163-183 /
-// 310-330 and its adjoint.  `__host__ __device__`, so that the expressions the gfx950 kernels evaluate also compile with g++
-// (tests/host_emul/gn_stage_emul.cpp, test infrastructure only -- the product has no CPU path).  DESIGN.md section 8e states the contract.
+// 310-330 and its adjoint, the resize to the skip's size of models.py:165-166 and its adjoint.  `__host__ __device__`, so that the
+// expressions the gfx950 kernels evaluate also compile with g++ (tests/host_emul/gn_stage_emul.cpp and gn_resize_emul.cpp, test
+// infrastructure only -- the product has no CPU path).  DESIGN.md section 8e states the contract.
 #pragma once
 
 #include "sgr_math.h"
@@ -93,6 +94,51 @@ SGR_HD void up_adjoint(const float (&g)[4][6], const float (&wr)[4], const float
     a = fmaf(wr[r], ha, a);
     b = fmaf(wr[r], hb, b);
   }
+}
+
+// ---- the resize to the skip's size (models.py:165-166 and its siblings, 185-186): F.interpolate(y, [ns_h, ns_w], mode='bilinear') with
+// n <= ns <= 2 n on either axis.  The rule is src_index at scale = (float)n / (float)ns, formed in fp32 on the host and passed in.
+// ORDER OF THE LERPS: a resized value is the lerp of its two COLUMN taps in either source row first, then the lerp of the two ROWS, as
+// torch's kernel does, and is an fp32 number before the 2x stage reads it (the reference materialises the map).
+struct RsTap { int i0, i1; float l0, l1; };
+SGR_HD RsTap rs_tap(int o, float scale, int n) {
+  RsTap t;
+  src_index(o, scale, n, t.i0, t.i1, t.l0, t.l1);
+  return t;
+}
+SGR_HD float rs_lerp(const RsTap& t, float a, float b) { return fmaf(t.l1, b, t.l0 * a); }
+// y at (rows tr.i0, tr.i1) x (columns tc.i0, tc.i1) -> the resized value
+SGR_HD float rs_value(float p00, float p01, float p10, float p11, const RsTap& tr, const RsTap& tc) {
+  return rs_lerp(tr, rs_lerp(tc, p00, p01), rs_lerp(tc, p10, p11));
+}
+// The adjoint, gathered: source index src receives from the resized indices o whose taps name it.  With n <= ns <= 2 n those are at most
+// four, and they lie in the window of kRsFan consecutive indices that starts at rs_adj_first (inv = (float)ns / (float)n; the window has
+// one spare index on either side of the real-valued bound, so the rounding of the bound cannot lose one --
+// tests/host_emul/gn_resize_emul.cpp checks that exhaustively).  An index of the window that does not name src, or lies outside the
+// map, carries the weight 0.
+constexpr int kRsFan = 6;
+SGR_HD int rs_adj_first(int src, float inv) { return (int)floorf(((float)src - 0.5f) * inv - 0.5f); }
+SGR_HD float rs_adj_w(int o, int src, float scale, int n, int ns) {
+  if (o < 0 || o >= ns) return 0.0f;
+  const RsTap t = rs_tap(o, scale, n);
+  return (t.i0 == src ? t.l0 : 0.0f) + (t.i1 == src ? t.l1 : 0.0f);
+}
+SGR_HD void rs_adj_weights(int src, float scale, float inv, int n, int ns, int& first, float (&w)[kRsFan]) {
+  first = rs_adj_first(src, inv);
+#pragma unroll
+  for (int k = 0; k < kRsFan; ++k) w[k] = rs_adj_w(first + k, src, scale, n, ns);
+}
+// a: the cotangent at the window's rows x columns (any finite number where the weight is 0).  A gather in a fixed order: columns, then rows.
+SGR_HD float rs_adjoint(const float (&a)[kRsFan][kRsFan], const float (&wr)[kRsFan], const float (&wc)[kRsFan]) {
+  float s = 0.0f;
+#pragma unroll
+  for (int r = 0; r < kRsFan; ++r) {
+    float h = wc[0] * a[r][0];
+#pragma unroll
+    for (int k = 1; k < kRsFan; ++k) h = fmaf(wc[k], a[r][k], h);
+    s = fmaf(wr[r], h, s);
+  }
+  return s;
 }
 
 }  // namespace sgr

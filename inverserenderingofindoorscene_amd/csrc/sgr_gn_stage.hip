@@ -1,6 +1,9 @@
 // The repeated stage of the reference's four network classes (models.py:87-346) around its convolution, on gfx950:
 //   plain   y  [B,C,H,W]        = relu(group_norm(x, G, weight, bias, eps))                                  (encoder0 / encoderLight, :122-127)
 //   upcat   up [B,C+Cs,2H,2W]   = interpolate(cat([y, skip], 1), scale_factor=2, mode='bilinear')            (decoder0 / decoderLight, :160-183)
+//   resize  the same two with relu(group_norm(x)) resized to [Hs, Ws] first, H <= Hs <= 2H, W <= Ws <= 2W: the decoders' stage against a
+//           skip of another size and the final stage's resize to the image (:165-166 and its siblings, :185-186, :312-333); second half
+//           of this file, entry points sgr_gn_resize_*
 // DESIGN.md section 8e states the contract; the per-element arithmetic is sgr_gn_stage.h.
 //
 // Forward, two launches: the moments of every (b, g) as double-precision (sum, sum of squares) partials, one per slice of the group, then
@@ -221,6 +224,42 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __r
   }
 }
 
+// The upsample's adjoint at the source pixels (i, 2jj) and (i, 2jj+1) of an H x W plane: gp is the cotangent's plane [2H, 2W], the six weight
+// sets are up_adj_sets' of either axis.  VEC: the four inner columns of a row as one 128-bit load (W even, 16-byte aligned cotangent).
+template <bool VEC>
+__device__ __forceinline__ void up_gather(const float* __restrict__ gp, int i, int jj, int H, int W, const float (&rl)[4], const float (&rm)[4],
+                                          const float (&rh)[4], const float (&cl)[4], const float (&cm)[4], const float (&chi)[4], float& a0,
+                                          float& a1) {
+  const int c0 = 2 * jj, OW = 2 * W, OH = 2 * H;
+  const bool two = c0 + 1 < W;
+  float gv[4][6];
+  float wr[4], wa[4], wb[4];
+  up_adj_pick(rl, rm, rh, i, H, wr);
+  up_adj_pick(cl, cm, chi, c0, W, wa);
+  up_adj_pick(cl, cm, chi, c0 + 1, W, wb);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) wb[k] = two ? wb[k] : 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int orow = 2 * i - 1 + k;
+    const bool in = orow >= 0 && orow < OH;
+    const float* row = gp + (long long)(in ? orow : 0) * OW;
+    const int o = 4 * jj;
+    gv[k][0] = in && o > 0 ? row[o - 1] : 0.0f;
+    if (VEC) {
+      Vec<4> t{{0.0f, 0.0f, 0.0f, 0.0f}};
+      if (in) t = *reinterpret_cast<const Vec<4>*>(row + o);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) gv[k][1 + u] = t.v[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) gv[k][1 + u] = in && o + u < OW ? row[o + u] : 0.0f;
+    }
+    gv[k][5] = in && o + 4 < OW ? row[o + 4] : 0.0f;
+  }
+  up_adjoint(gv, wr, wa, wb, a0, a1);
+}
+
 // Backward pass 1 over the channels [c_begin, c_begin + gridDim.y) of cat([y, skip]).  UP: g is [B,C+Cs,2H,2W] and the adjoint is gathered;
 // otherwise g is [B,C,H,W] and taken as it is.  ch < C: dy = (y > 0) adjoint, stored to `dy` (if given) and summed; ch >= C: dskip = adjoint.
 template <bool VEC, bool UP>
@@ -254,32 +293,7 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __
     const bool two = c0 + 1 < W;
     float a0, a1;
     if (UP) {
-      float gv[4][6];
-      float wr[4], wa[4], wb[4];
-      up_adj_pick(rl, rm, rh, i, H, wr);
-      up_adj_pick(cl, cm, chi, c0, W, wa);
-      up_adj_pick(cl, cm, chi, c0 + 1, W, wb);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) wb[k] = two ? wb[k] : 0.0f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int orow = 2 * i - 1 + k;
-        const bool in = orow >= 0 && orow < OH;
-        const float* row = gp + (long long)(in ? orow : 0) * OW;
-        const int o = 4 * jj;
-        gv[k][0] = in && o > 0 ? row[o - 1] : 0.0f;
-        if (VEC) {
-          Vec<4> t{{0.0f, 0.0f, 0.0f, 0.0f}};
-          if (in) t = *reinterpret_cast<const Vec<4>*>(row + o);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) gv[k][1 + u] = t.v[u];
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) gv[k][1 + u] = in && o + u < OW ? row[o + u] : 0.0f;
-        }
-        gv[k][5] = in && o + 4 < OW ? row[o + 4] : 0.0f;
-      }
-      up_adjoint(gv, wr, wa, wb, a0, a1);
+      up_gather<VEC>(gp, i, jj, H, W, rl, rm, rh, cl, cm, chi, a0, a1);
     } else {
       a0 = gp[(long long)i * W + c0];
       a1 = two ? gp[(long long)i * W + c0 + 1] : 0.0f;
@@ -393,6 +407,228 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __
       for (int u = 0; u < 4; ++u)
         if (p + u < HW) op[p + u] = dv.v[u];
     }
+  }
+}
+
+// ---- the resize-to-skip forms (models.py:165-166 and its siblings; 185-186): y is resized from H x W to the skip's Hs x Ws before the
+// concatenation, H <= Hs <= 2H and W <= Ws <= 2W.  The arithmetic is the rs_* part of sgr_gn_stage.h; sch / scw are the fp32 scales
+// (float)H / (float)Hs and (float)W / (float)Ws, formed on the host.  SAMEW (W == Ws, the usual case: only the floor-halved height is off):
+// the scale is exactly 1, a column's second tap has the weight 0 and is not loaded -- the same bits.
+
+// relu(gn(.)) of the x plane at the taps (tr) x (tc): the resized value
+template <bool SAMEW>
+__device__ __forceinline__ float rs_gn_value(const float* __restrict__ src, unsigned sth, unsigned stw, const RsTap& tr, const RsTap& tc, float mh, float ml,
+                                             float rstd, float wc, float bc) {
+  auto y = [&](int r, int c) { return fmaxf(gn_pre(gn_xhat(src[(unsigned)r * sth + (unsigned)c * stw], mh, ml, rstd), wc, bc), 0.0f); };
+  const float p00 = y(tr.i0, tc.i0), p10 = y(tr.i1, tc.i0);
+  const float p01 = SAMEW ? p00 : y(tr.i0, tc.i1), p11 = SAMEW ? p10 : y(tr.i1, tc.i1);
+  return rs_value(p00, p01, p10, p11, tr, tc);
+}
+
+// resize + upcat: gn_apply_up_kernel at the skip's resolution, the 3 x 4 neighbourhood of a normalised channel formed from x on the fly
+template <bool VEC, bool SAMEW>
+__global__ __launch_bounds__(kGThreads) void gn_apply_rsup_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
+                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                  const double* __restrict__ partials, float* __restrict__ stats,
+                                                                  float* __restrict__ out, int C, int Cs, int cpg, int H, int W, int Hs, int Ws,
+                                                                  float sch, float scw, int S, float eps) {
+  __shared__ float sh[4];
+  const int ch = blockIdx.y, b = blockIdx.z;
+  const bool norm = ch < C;      // uniform in the workgroup
+  float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
+  const float* src;
+  GnStrides st;
+  if (norm) {
+    const int G = C / cpg, g = ch / cpg;
+    gn_group_stat(partials, b * G + g, S, (double)cpg * H * W, eps, sh);
+    mh = sh[0]; ml = sh[1]; rstd = sh[2];
+    if (blockIdx.x == 0 && ch == g * cpg && threadIdx.x == 0) {
+      float* o = stats + 4 * ((long long)b * G + g);
+      o[0] = mh; o[1] = ml; o[2] = rstd; o[3] = sh[3];
+    }
+    wc = weight[ch]; bc = bias[ch];
+    src = x + (long long)b * xs.b + (long long)ch * xs.c;
+    st = xs;
+  } else {
+    src = skip + (long long)b * ss.b + (long long)(ch - C) * ss.c;
+    st = ss;
+  }
+  const int W2 = (Ws + 1) >> 1, OW = 2 * Ws;
+  float* op = out + ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
+  const unsigned sth = (unsigned)st.h, stw = (unsigned)st.w;      // in-plane offsets fit 31 bits (checked on the host)
+  const UpTaps taps = up_taps();
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
+  int i = q0 / W2, jj = q0 - i * W2;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < Hs; ++r) {
+    const int c0 = 2 * jj;
+    const int rr[3] = {i > 0 ? i - 1 : 0, i, i + 1 < Hs ? i + 1 : Hs - 1};
+    const int cc[4] = {c0 > 0 ? c0 - 1 : 0, c0, c0 + 1 < Ws ? c0 + 1 : Ws - 1, c0 + 2 < Ws ? c0 + 2 : Ws - 1};
+    float v[3][4];
+    if (norm) {
+      RsTap tcol[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) tcol[k] = rs_tap(cc[k], scw, W);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const RsTap trow = rs_tap(rr[a], sch, H);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[a][k] = rs_gn_value<SAMEW>(src, sth, stw, trow, tcol[k], mh, ml, rstd, wc, bc);
+      }
+    } else {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[a][k] = src[(unsigned)rr[a] * sth + (unsigned)cc[k] * stw];
+    }
+    const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
+    Vec<4> top, bot;
+    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top.v, bot.v);
+    float* o0 = op + (long long)(2 * i) * OW + 4 * jj;
+    if (VEC) {
+      *reinterpret_cast<Vec<4>*>(o0) = top;
+      *reinterpret_cast<Vec<4>*>(o0 + OW) = bot;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * jj + k < OW) { o0[k] = top.v[k]; o0[OW + k] = bot.v[k]; }
+    }
+    i += di;
+    jj += dj;
+    if (jj >= W2) { jj -= W2; ++i; }
+  }
+}
+
+// resize alone (the final stage): a thread makes the columns 4jq .. 4jq+3 of resized row i.  VEC: 128-bit stores (Ws % 4 == 0, aligned result).
+template <bool VEC, bool SAMEW>
+__global__ __launch_bounds__(kGThreads) void gn_apply_rs_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+                                                                const float* __restrict__ bias, const double* __restrict__ partials,
+                                                                float* __restrict__ stats, float* __restrict__ out, int C, int cpg, int H, int W, int Hs,
+                                                                int Ws, float sch, float scw, int S, float eps) {
+  __shared__ float sh[4];
+  const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
+  gn_group_stat(partials, b * G + g, S, (double)cpg * H * W, eps, sh);
+  const float mh = sh[0], ml = sh[1], rstd = sh[2];
+  if (blockIdx.x == 0 && c == g * cpg && threadIdx.x == 0) {
+    float* o = stats + 4 * ((long long)b * G + g);
+    o[0] = mh; o[1] = ml; o[2] = rstd; o[3] = sh[3];
+  }
+  const float wc = weight[c], bc = bias[c];
+  const float* src = x + (long long)b * xs.b + (long long)c * xs.c;
+  float* op = out + ((long long)b * C + c) * (long long)Hs * Ws;
+  const unsigned sth = (unsigned)xs.h, stw = (unsigned)xs.w;
+  const int W4 = (Ws + 3) >> 2;
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W4, dj = kGThreads - di * W4;
+  int i = q0 / W4, jq = q0 - i * W4;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < Hs; ++r) {
+    const RsTap trow = rs_tap(i, sch, H);
+    Vec<4> q;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = 4 * jq + k < Ws ? 4 * jq + k : Ws - 1;
+      q.v[k] = rs_gn_value<SAMEW>(src, sth, stw, trow, rs_tap(col, scw, W), mh, ml, rstd, wc, bc);
+    }
+    float* o0 = op + (long long)i * Ws + 4 * jq;
+    if (VEC) {
+      *reinterpret_cast<Vec<4>*>(o0) = q;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * jq + k < Ws) o0[k] = q.v[k];
+    }
+    i += di;
+    jq += dj;
+    if (jq >= W4) { jq -= W4; ++i; }
+  }
+}
+
+// Backward, step 1 of the resize + upcat form: the upsample's adjoint at the skip's resolution, unmasked, over the channels
+// [c_begin, c_begin + gridDim.y) of the concatenation.  ch < C goes to `da` [B,C,Hs,Ws] (workspace), ch >= C is dskip.
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_up_adjoint_kernel(const float* __restrict__ g, float* __restrict__ da, float* __restrict__ dskip, int C,
+                                                                  int Cs, int Hs, int Ws, int c_begin) {
+  const int ch = c_begin + blockIdx.y, b = blockIdx.z;
+  const int W2 = (Ws + 1) >> 1;
+  const float* gp = g + ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
+  float* dst = ch < C ? da + ((long long)b * C + ch) * Hs * Ws : dskip + ((long long)b * Cs + (ch - C)) * Hs * Ws;
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];
+  up_adj_sets(Hs, rl, rm, rh);
+  up_adj_sets(Ws, cl, cm, chi);
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
+  int i = q0 / W2, jj = q0 - i * W2;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < Hs; ++r) {
+    float a0, a1;
+    up_gather<VEC>(gp, i, jj, Hs, Ws, rl, rm, rh, cl, cm, chi, a0, a1);
+    dst[(long long)i * Ws + 2 * jj] = a0;
+    if (2 * jj + 1 < Ws) dst[(long long)i * Ws + 2 * jj + 1] = a1;
+    i += di;
+    jj += dj;
+    if (jj >= W2) { jj -= W2; ++i; }
+  }
+}
+
+// Backward, the resize's adjoint gathered at the source resolution, one source pixel per thread and round: a [B,C,Hs,Ws] is step 1's `da`
+// or, in the form without a skip, the cotangent itself.  dy = (y > 0) adjoint, stored (if given) and summed as gn_bwd_pass1_kernel does:
+// the fold and pass 2 that follow are the existing ones.  FC: the columns of the window (1 with W == Ws: the pixel's own column).
+template <int FC>
+__global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float* __restrict__ a, const float* __restrict__ x, GnStrides xs,
+                                                                    const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                    const float* __restrict__ stats, float* __restrict__ dy, double* __restrict__ partials,
+                                                                    int C, int cpg, int H, int W, int Hs, int Ws, float sch, float scw, float inh,
+                                                                    float inw) {
+  __shared__ double lds[2 * kGThreads / 64];
+  const int ch = blockIdx.y, b = blockIdx.z, P = gridDim.x;
+  const float* st = stats + 4 * ((long long)b * (C / cpg) + ch / cpg);
+  const float mh = st[0], ml = st[1], rstd = st[2], wc = weight[ch], bc = bias[ch];
+  const float* xp = x + (long long)b * xs.b + (long long)ch * xs.c;
+  const float* ap = a + ((long long)b * C + ch) * (long long)Hs * Ws;
+  float* dst = dy ? dy + ((long long)b * C + ch) * H * W : nullptr;
+  const unsigned sh = (unsigned)xs.h, sw = (unsigned)xs.w;      // in-plane offsets fit 31 bits (checked on the host)
+  double s1 = 0.0, s2 = 0.0;
+  const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W, dj = kGThreads - di * W;
+  int i = q0 / W, j = q0 - i * W;
+#pragma unroll 1
+  for (int r = 0; r < kGRounds && i < H; ++r) {
+    int fr, fc;
+    float wr[kRsFan], wcol[kRsFan];
+    rs_adj_weights(i, sch, inh, H, Hs, fr, wr);
+    if (FC == kRsFan) rs_adj_weights(j, scw, inw, W, Ws, fc, wcol);
+    float d = 0.0f;
+    if (FC == kRsFan) {
+      float av[kRsFan][kRsFan];
+#pragma unroll
+      for (int kr = 0; kr < kRsFan; ++kr) {
+        const int row = fr + kr < 0 ? 0 : fr + kr < Hs ? fr + kr : Hs - 1;
+#pragma unroll
+        for (int kc = 0; kc < kRsFan; ++kc) {
+          const int col = fc + kc < 0 ? 0 : fc + kc < Ws ? fc + kc : Ws - 1;
+          av[kr][kc] = ap[row * Ws + col];
+        }
+      }
+      d = rs_adjoint(av, wr, wcol);
+    } else {
+#pragma unroll
+      for (int kr = 0; kr < kRsFan; ++kr) {
+        const int row = fr + kr < 0 ? 0 : fr + kr < Hs ? fr + kr : Hs - 1;
+        d = fmaf(wr[kr], ap[row * Ws + j], d);
+      }
+    }
+    const float xh = gn_xhat(xp[(unsigned)i * sh + (unsigned)j * sw], mh, ml, rstd);
+    d = gn_pre(xh, wc, bc) > 0.0f ? d : 0.0f;
+    s1 += (double)d;
+    s2 = fma((double)d, (double)xh, s2);
+    if (dst) dst[i * W + j] = d;
+    i += di;
+    j += dj;
+    if (j >= W) { j -= W; ++i; }
+  }
+  block_sum2(s1, s2, lds);
+  if (threadIdx.x == 0) {
+    double* o = partials + 2 * (((long long)b * C + ch) * P + blockIdx.x);
+    o[0] = s1;
+    o[1] = s2;
   }
 }
 
@@ -513,4 +749,120 @@ extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* wei
     }
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_bwd");
+}
+
+// ---- resize-to-skip entry points ------------------------------------------------------------------------------------------------------------
+
+namespace sgr {
+static bool rs_domain(int H, int W, int Hs, int Ws) { return Hs >= H && Hs <= 2 * H && Ws >= W && Ws <= 2 * W; }
+// slices of a plane in the resize backward's gather: one source pixel per thread and round
+static int rs_bwd_slices(int H, int W) { return g_rounds_grid((long long)H * W); }
+
+#define RS_CHECK_SIZES(who)                                                                                              \
+  GN_CHECK_SIZES(who);                                                                                                   \
+  SGR_REQUIRE(Hs > 0 && Ws > 0, who ": non-positive size");                                                              \
+  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), who ": outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");            \
+  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), who ": Hs * Ws out of range")
+}  // namespace sgr
+
+extern "C" long long sgr_gn_resize_workspace_floats(int B, int C, int G, int H, int W, int Hs, int Ws, int upcat, int backward) {
+  if (!(B > 0 && C > 0 && G > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0) || C % G != 0 || !rs_domain(H, W, Hs, Ws)) return 0;
+  const long long HW = (long long)H * W;
+  if (!backward) return 4ll * B * G * gn_slices((long long)(C / G) * HW);
+  // partials (doubles), the group coefficients, the masked adjoint at the source resolution, then (upcat) the upsample's adjoint
+  return 4ll * B * C * rs_bwd_slices(H, W) + g_coef_floats(B, G) + (long long)B * C * HW + (upcat ? (long long)B * C * Hs * Ws : 0);
+}
+
+extern "C" int sgr_gn_resize_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
+                                 int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides, const long long* skip_strides,
+                                 float eps, void* stream) {
+  SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, "sgr_gn_resize_fwd: NULL tensor");
+  SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), "sgr_gn_resize_fwd: skip and its channel count do not agree");
+  RS_CHECK_SIZES("sgr_gn_resize_fwd");
+  SGR_REQUIRE(eps > 0.0f, "sgr_gn_resize_fwd: eps must be positive");
+  SGR_SUPPORTED(g_plane_fits(x_strides, H, W) && (!skip || g_plane_fits(skip_strides, Hs, Ws)), "sgr_gn_resize_fwd: negative or out-of-range plane strides");
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_fwd: the workspace must be 8-byte aligned");
+  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
+  const GnStrides ss = skip ? GnStrides{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]} : GnStrides{0, 0, 0, 0};
+  const int cpg = C / G, HW = H * W;
+  const long long n = (long long)cpg * HW;
+  const int S = gn_slices(n);
+  const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws;
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
+  if (g_plane_vec(x, xs, H, W))
+    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  else
+    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  const bool samew = W == Ws;
+#define RS_LAUNCH(kernel, vec, grid, ...)                                                                                   \
+  do {                                                                                                                      \
+    if (vec) {                                                                                                              \
+      if (samew) hipLaunchKernelGGL((kernel<true, true>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                       \
+      else hipLaunchKernelGGL((kernel<true, false>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                            \
+    } else {                                                                                                                \
+      if (samew) hipLaunchKernelGGL((kernel<false, true>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                      \
+      else hipLaunchKernelGGL((kernel<false, false>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                           \
+    }                                                                                                                       \
+  } while (0)
+  if (!skip) {
+    const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 3) / 4)), C, B);
+    RS_LAUNCH(gn_apply_rs_kernel, Ws % 4 == 0 && aligned16({out}), grid, x, xs, weight, bias, partials, stats, out, C, cpg, H, W, Hs, Ws, sch, scw, S, eps);
+  } else {
+    const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 1) / 2)), C + Cs, B);
+    RS_LAUNCH(gn_apply_rsup_kernel, Ws % 2 == 0 && aligned16({out}), grid, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, Hs, Ws, sch,
+              scw, S, eps);
+  }
+#undef RS_LAUNCH
+  return sgr_check((int)hipGetLastError(), "sgr_gn_resize_fwd");
+}
+
+extern "C" int sgr_gn_resize_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
+                                 float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
+                                 const long long* x_strides, void* stream) {
+  SGR_REQUIRE(g, "sgr_gn_resize_bwd: NULL cotangent");
+  SGR_REQUIRE(dx || dweight || dbias || dskip, "sgr_gn_resize_bwd: no gradient requested");
+  const bool side = dx || dweight || dbias;      // anything behind the normalisation
+  SGR_REQUIRE(!side || (x && weight && bias && stats && workspace && x_strides), "sgr_gn_resize_bwd: NULL tensor");
+  SGR_REQUIRE(!dskip || Cs > 0, "sgr_gn_resize_bwd: dskip requested without skip channels");
+  RS_CHECK_SIZES("sgr_gn_resize_bwd");
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_bwd: the workspace must be 8-byte aligned");
+  SGR_SUPPORTED(!side || g_plane_fits(x_strides, H, W), "sgr_gn_resize_bwd: negative or out-of-range plane strides");
+  const bool up = Cs > 0;
+  const int cpg = C / G, HW = H * W, P = rs_bwd_slices(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  double* partials = reinterpret_cast<double*>(workspace);
+  float* coef = side ? workspace + 4ll * B * C * P : nullptr;
+  float* dy = side ? coef + g_coef_floats(B, G) : nullptr;
+  float* da = side && up ? dy + (long long)B * C * HW : nullptr;
+  if (up) {      // step 1: the upsample's adjoint of the channels somebody wants
+    const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
+    const dim3 grid(g_bwd_slices(Hs, Ws), c_end - c_begin, B);
+    if (Ws % 2 == 0 && aligned16({g}))
+      hipLaunchKernelGGL(gn_up_adjoint_kernel<true>, grid, dim3(kGThreads), 0, st, g, da, dskip, C, Cs, Hs, Ws, c_begin);
+    else
+      hipLaunchKernelGGL(gn_up_adjoint_kernel<false>, grid, dim3(kGThreads), 0, st, g, da, dskip, C, Cs, Hs, Ws, c_begin);
+  }
+  if (side) {
+    const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
+    const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws, inh = (float)Hs / (float)H, inw = (float)Ws / (float)W;
+    const float* a = up ? da : g;
+    float* dyo = dx ? dy : nullptr;
+    const dim3 grid1(P, C, B);
+    if (W == Ws)
+      hipLaunchKernelGGL(gn_rs_bwd_pass1_kernel<1>, grid1, dim3(kGThreads), 0, st, a, x, xs, weight, bias, stats, dyo, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
+    else
+      hipLaunchKernelGGL(gn_rs_bwd_pass1_kernel<kRsFan>, grid1, dim3(kGThreads), 0, st, a, x, xs, weight, bias, stats, dyo, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
+    const int jobs = B * G + ((dweight || dbias) ? C : 0);
+    hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(jobs), dim3(64), 0, st, partials, weight, coef, dweight, dbias, B, C, cpg, P, (double)cpg * HW);
+    if (dx) {
+      const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
+      if (g_plane_vec(x, xs, H, W) && aligned16({dy, dx}))
+        hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+      else
+        hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+    }
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_gn_resize_bwd");
 }

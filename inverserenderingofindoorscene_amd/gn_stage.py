@@ -5,18 +5,22 @@
   ``group_norm_relu_upcat(x, weight, bias, num_groups, skip, eps)``   ``F.interpolate(torch.cat([F.relu(dgnK(x)), skip], 1), scale_factor=2,
                                                                       mode='bilinear')`` of ``models.decoder0`` / ``decoderLight``
                                                                       (models.py:160-183, 307-330): what ``dconv{K+1}`` reads
-  ``GroupNormReLU(num_groups, num_channels, eps)``                    the module form; ``weight`` / ``bias`` load a checkpoint's ``gnK.*``
+  ``group_norm_relu_resize_upcat(x, weight, bias, num_groups, skip, eps)``   the same stage with a ``skip`` of another size: the normalised
+                                                                      map is resized to it first (models.py:165-166 and its siblings)
+  ``group_norm_relu_resize(x, weight, bias, num_groups, size, eps)``  ``F.interpolate(F.relu(dgn6(x)), size, mode='bilinear')``: the final
+                                                                      stage's resize to the image (models.py:183-186, 330-333)
+  ``GroupNormReLU(num_groups, num_channels, eps, resize=False)``      the module form; ``weight`` / ``bias`` load a checkpoint's ``gnK.*``
 
 Eager PyTorch spends four launches forward on a decoder stage (GroupNorm, ReLU, ``cat``, ``upsample_bilinear2d``) and keeps three maps for
-the backward; here it is two launches forward and three backward, and ``x`` with the per-group statistics is all that is kept.  DESIGN.md
-section 8e states the arithmetic."""
+the backward; here it is two launches forward and three backward, and ``x`` with the per-group statistics is all that is kept.  The resize
+forms are two launches forward and four (without a skip: three) backward and keep the same.  DESIGN.md section 8e states the arithmetic."""
 from __future__ import annotations
 
 import torch
 
 from . import ops as _ops      # noqa: F401  (loads libsgrender_torch.so)
 
-__all__ = ["group_norm_relu", "group_norm_relu_upcat", "GroupNormReLU"]
+__all__ = ["group_norm_relu", "group_norm_relu_upcat", "group_norm_relu_resize", "group_norm_relu_resize_upcat", "GroupNormReLU"]
 
 _sg = torch.ops.sgrender
 
@@ -41,23 +45,55 @@ def group_norm_relu_upcat(x, weight, bias, num_groups: int, skip, eps: float = 1
     return _sg.gn_stage(x, weight, bias, skip, int(num_groups), float(eps))[0]
 
 
+def group_norm_relu_resize_upcat(x, weight, bias, num_groups: int, skip, eps: float = 1e-5):
+    """``F.interpolate(torch.cat([F.interpolate(group_norm_relu(x, ...), [Hs, Ws], mode='bilinear'), skip], 1), scale_factor=2,
+    mode='bilinear')``: ``[B, C + Cs, 2Hs, 2Ws]`` from ``x [B,C,H,W]`` and ``skip [B,Cs,Hs,Ws]`` -- a decoder stage with the reference's
+    ``if`` taken (models.py:165-166, 312-313 and their siblings).  Per axis ``H <= Hs <= 2H`` and ``W <= Ws <= 2W``; anything else raises and
+    stays the caller's composition.  With ``(Hs, Ws) == (H, W)`` the reference skips the resize and this is :func:`group_norm_relu_upcat`,
+    bit for bit.  Differentiable with respect to ``x``, ``weight``, ``bias`` and ``skip``; the node keeps ``x``, the parameters and the
+    per-group statistics, no resized or concatenated map and no ``skip``."""
+    if skip is None:
+        raise RuntimeError("sgrender: group_norm_relu_resize_upcat: skip is None; group_norm_relu_resize is the form without a skip")
+    if skip.dim() == 4 and x.dim() == 4 and tuple(skip.shape[2:]) == tuple(x.shape[2:]):
+        return _sg.gn_stage(x, weight, bias, skip, int(num_groups), float(eps))[0]
+    h, w = (int(skip.shape[2]), int(skip.shape[3])) if skip.dim() == 4 else (0, 0)
+    return _sg.gn_resize(x, weight, bias, skip, int(num_groups), h, w, float(eps))[0]
+
+
+def group_norm_relu_resize(x, weight, bias, num_groups: int, size, eps: float = 1e-5):
+    """``F.interpolate(group_norm_relu(x, ...), size, mode='bilinear')``: ``[B, C, Hs, Ws]`` for ``size = (Hs, Ws)`` in the same domain -- the
+    final stage's resize to the image (models.py:185-186, 332-333).  ``size == (H, W)`` is :func:`group_norm_relu`, bit for bit."""
+    h, w = (int(v) for v in size)
+    if x.dim() == 4 and (h, w) == tuple(x.shape[2:]):
+        return _sg.gn_stage(x, weight, bias, None, int(num_groups), float(eps))[0]
+    return _sg.gn_resize(x, weight, bias, None, int(num_groups), h, w, float(eps))[0]
+
+
 class GroupNormReLU(torch.nn.Module):
     """``nn.GroupNorm(num_groups, num_channels, eps)`` followed by ReLU as one operator.  The parameters are named as ``nn.GroupNorm``'s, so
     ``load_state_dict`` takes a reference checkpoint's ``gnK.weight`` / ``gnK.bias`` (``dgnK.*``) under the same prefix.
-    ``forward(x)`` is :func:`group_norm_relu`; ``forward(x, skip)`` is :func:`group_norm_relu_upcat`."""
+    ``forward(x)`` is :func:`group_norm_relu`; ``forward(x, skip)`` is :func:`group_norm_relu_upcat`.  With ``resize=True`` a ``skip`` of
+    another size is accepted (:func:`group_norm_relu_resize_upcat`) and ``forward(x, size=(h, w))`` is :func:`group_norm_relu_resize`."""
 
-    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5):
+    def __init__(self, num_groups: int, num_channels: int, eps: float = 1e-5, resize: bool = False):
         super().__init__()
         if num_channels % num_groups != 0:
             raise ValueError(f"sgrender: GroupNormReLU: num_channels {num_channels} is not a multiple of num_groups {num_groups}")
         self.num_groups, self.num_channels, self.eps = int(num_groups), int(num_channels), float(eps)
+        self.resize = bool(resize)
         self.weight = torch.nn.Parameter(torch.ones(num_channels))
         self.bias = torch.nn.Parameter(torch.zeros(num_channels))
 
-    def forward(self, x, skip=None):
+    def forward(self, x, skip=None, size=None):
+        if size is not None:
+            if not self.resize or skip is not None:
+                raise RuntimeError("sgrender: GroupNormReLU: size= is the final-stage form of resize=True and takes no skip")
+            return group_norm_relu_resize(x, self.weight, self.bias, self.num_groups, size, self.eps)
         if skip is None:
             return group_norm_relu(x, self.weight, self.bias, self.num_groups, self.eps)
+        if self.resize:
+            return group_norm_relu_resize_upcat(x, self.weight, self.bias, self.num_groups, skip, self.eps)
         return group_norm_relu_upcat(x, self.weight, self.bias, self.num_groups, skip, self.eps)
 
     def extra_repr(self):
-        return f"{self.num_groups}, {self.num_channels}, eps={self.eps}"
+        return f"{self.num_groups}, {self.num_channels}, eps={self.eps}" + (", resize=True" if self.resize else "")

@@ -5,8 +5,9 @@ at batch 16, forward and forward + backward.
     python tools/gn_stage_bench.py [--reps 80] [--warmup 10] [--out FILE.json]
     rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --profile     # the fused calls only, few repetitions
 
-At 240x320 ``decoder0``'s second stage works at 14x20 against a 15x20 skip: the reference's resize branch, which stays the caller's, so that
-stage is timed in the plain form (GroupNorm + ReLU, the part the operator covers there).
+At 240x320 ``decoder0``'s second stage works at 14x20 against a 15x20 skip: the reference's resize branch.  ``dec_dgn2_plain`` times the plain
+form there (GroupNorm + ReLU alone, as before the resize was fused); ``dec_dgn2``, ``light_dgn2``, ``light_dgn3`` and ``dec_final`` are the real
+stages through sgr.group_norm_relu_resize_upcat / sgr.group_norm_relu_resize against the reference's composition with its ``if`` taken.
 
 Method: device events around each call, warm-up, median of >= 80, the fused call and the eager form alternating in one process; the
 min-max spread of the repetitions is printed beside each median.  The algorithmic byte counts come from the shapes:
@@ -26,23 +27,34 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM_TBPS = 8.0
 B = 16
-# (name, C, G, H, W, Cs)
+# (name, C, G, H, W, Cs) and, for a resize stage, the skip's (Hs, Ws)
 STAGES = [("enc_gn1", 64, 4, 120, 160, 0), ("enc_gn2", 128, 8, 60, 80, 0), ("enc_gn3", 256, 16, 30, 40, 0), ("enc_gn4", 256, 16, 15, 20, 0),
           ("enc_gn5", 512, 32, 7, 10, 0), ("enc_gn6", 1024, 64, 7, 10, 0),
           ("dec_dgn1", 512, 32, 7, 10, 512), ("dec_dgn2_plain", 256, 16, 14, 20, 0), ("dec_dgn3", 256, 16, 30, 40, 256),
-          ("dec_dgn4", 128, 8, 60, 80, 128), ("dec_dgn5", 64, 4, 120, 160, 64)]
+          ("dec_dgn4", 128, 8, 60, 80, 128), ("dec_dgn5", 64, 4, 120, 160, 64),
+          ("dec_dgn2", 256, 16, 14, 20, 256, (15, 20)), ("light_dgn2", 512, 32, 6, 10, 512, (7, 10)), ("light_dgn3", 256, 16, 14, 20, 256, (15, 20)),
+          ("dec_final", 64, 4, 212, 320, 0, (213, 320))]
 
 
-def eager_stage(x, w, b, G, skip):
+def eager_stage(x, w, b, G, skip, size=None):
     y = F.relu(F.group_norm(x, G, w, b, 1e-5), True)
+    if size is not None:
+        y = F.interpolate(y, list(size), mode="bilinear")
     if skip is None:
         return y
     return F.interpolate(torch.cat([y, skip], dim=1), scale_factor=2, mode="bilinear")
 
 
-def nbytes(C, H, W, Cs):
+def nbytes(C, H, W, Cs, size=None):
     """-> (forward, backward) algorithmic bytes at batch B"""
     m = B * H * W * 4
+    if size is not None:
+        ms = B * size[0] * size[1] * 4
+        if Cs == 0:      # fwd: x twice, the resized map out; bwd: gather reads g, x, writes dy; pass 2 reads dy, x, writes dx
+            return 2 * C * m + C * ms, C * ms + 5 * C * m
+        fwd = 2 * C * m + Cs * ms + 4 * (C + Cs) * ms
+        # step 1: g -> da, dskip; gather: da, x -> dy; pass 2: dy, x -> dx
+        return fwd, 4 * (C + Cs) * ms + (C + Cs) * ms + C * ms + 5 * C * m
     if Cs == 0:
         return (2 * C + C) * m, (C + C + C + C + C) * m          # bwd: pass 1 reads g, x; pass 2 reads g, x, writes dx
     fwd = (2 * C + Cs + 4 * (C + Cs)) * m
@@ -80,16 +92,21 @@ def main():
         raise SystemExit("gn_stage_bench needs a GPU")
     reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
     rec = {"device": torch.cuda.get_device_name(0), "reps": reps, "batch": B, "ms": {}, "bytes": {}}
-    for name, C, G, H, W, Cs in STAGES:
+    for name, C, G, H, W, Cs, *rest in STAGES:
+        size = rest[0] if rest else None
+        Hs, Ws = size if size else (H, W)
         g = torch.Generator().manual_seed(len(name) + C)
         x = torch.randn(B, C, H, W, generator=g).cuda().requires_grad_(True)
         w = torch.randn(C, generator=g).cuda().requires_grad_(True)
         b = (0.3 * torch.randn(C, generator=g)).cuda().requires_grad_(True)
-        skip = torch.randn(B, Cs, H, W, generator=g).cuda().requires_grad_(True) if Cs else None
-        ct = torch.randn(B, C + Cs, 2 * H, 2 * W, generator=g).cuda() if Cs else torch.randn(B, C, H, W, generator=g).cuda()
+        skip = torch.randn(B, Cs, Hs, Ws, generator=g).cuda().requires_grad_(True) if Cs else None
+        ct = torch.randn(B, C + Cs, 2 * Hs, 2 * Ws, generator=g).cuda() if Cs else torch.randn(B, C, Hs, Ws, generator=g).cuda()
         leaves = [t for t in (x, w, b, skip) if t is not None]
-        fused = (lambda: sgr.group_norm_relu_upcat(x, w, b, G, skip)) if Cs else (lambda: sgr.group_norm_relu(x, w, b, G))
-        eager = lambda: eager_stage(x, w, b, G, skip)
+        if size:
+            fused = (lambda: sgr.group_norm_relu_resize_upcat(x, w, b, G, skip)) if Cs else (lambda: sgr.group_norm_relu_resize(x, w, b, G, size))
+        else:
+            fused = (lambda: sgr.group_norm_relu_upcat(x, w, b, G, skip)) if Cs else (lambda: sgr.group_norm_relu(x, w, b, G))
+        eager = lambda: eager_stage(x, w, b, G, skip, size)
 
         def fwd(f):
             def run():
@@ -103,7 +120,7 @@ def main():
         if not args.profile:
             fns.update(eager_fwd=fwd(eager), eager_fwd_bwd=fwdbwd(eager))
         t = timed(fns, reps, warm)
-        b_fwd, b_bwd = nbytes(C, H, W, Cs)
+        b_fwd, b_bwd = nbytes(C, H, W, Cs, size)
         rec["bytes"][name] = dict(forward=b_fwd, backward=b_bwd)
         for k, v in t.items():
             med = statistics.median(v)
