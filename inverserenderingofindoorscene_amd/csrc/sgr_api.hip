@@ -36,20 +36,19 @@ int sgr_check(int hip_rc, const char* who) {
 extern "C" int sgr_abi_version(void) { return SGR_ABI_VERSION; }
 extern "C" const char* sgr_last_error(void) { return sgr::g_err; }
 
-extern "C" int sgr_dirs_padded(int J) { return (J + 31) / 32 * 32; }
-static int rows_padded(int eh) { return (eh + 1) / 2 * 2; }
-extern "C" int sgr_dirs_floats(int eh, int ew) { return 4 * sgr_dirs_padded(eh * ew) + 8 * rows_padded(eh) + 8 * ew; }
+extern "C" int sgr_dirs_padded(int J) { return sgr::dirs_padded(J); }
+extern "C" int sgr_dirs_floats(int eh, int ew) { return sgr::dir_layout(eh, ew).floats; }
 
 // models.py:353-363 (output2env.__init__) and models.py:437-452 (renderingLayer.__init__):
 // float64 arithmetic, results stored as float32; the evaluation order of the scalar
 // expressions follows the Python source so the rounded values are the same.
 extern "C" int sgr_fill_direction_table(float* out, int eh, int ew) {
   SGR_REQUIRE(out && eh > 0 && ew > 0, "sgr_fill_direction_table: bad argument");
-  const int J = eh * ew, Jp = sgr_dirs_padded(J);
-  memset(out, 0, sizeof(float) * (size_t)sgr_dirs_floats(eh, ew));
+  const sgr::DirLayout t = sgr::dir_layout(eh, ew);
+  memset(out, 0, sizeof(float) * (size_t)t.floats);
   // separable form: l_j = (s_e ca_a, s_e sa_a, c_e); rows (s, c, omega, s^2, 2sc, c^2), cols (ca, sa, ca^2, 2 ca sa, sa^2)
-  float* rows = out + 4 * (size_t)Jp;
-  float* cols = rows + 8 * (size_t)rows_padded(eh);
+  float* rows = out + t.rows;
+  float* cols = out + t.cols;
   for (int e = 0; e < eh; ++e) {
     const double el = (((double)e + 0.5) / (double)eh) * M_PI / 2.0;
     const double sd = sin(el), cd = cos(el);

@@ -17,6 +17,7 @@
 #include "sgr_launch.h"
 #include <string.h>
 #include "sgr_pk.inl"
+#include "sgr_layer_launch.h"
 
 #ifndef SGR_TJ
 #define SGR_TJ 32
@@ -208,17 +209,16 @@ static int sgbwd_launch_k(const Args& a, hipStream_t st) {
 template <bool HAS_GENV, bool HAS_RENDER, int EW, bool HEADS = false>
 static int sgbwd_pk_launch_ew(const Args& a, hipStream_t st) {
   const int ng = (a.K + 11) / 12;
-  const unsigned tiles = (unsigned)(a.bn * ((a.R * a.C + kPx - 1) / kPx));
+  const unsigned tiles = half_wave_grid(a.bn, a.R, a.C).x;
   const dim3 grid(ng == 1 ? tiles : ((tiles + 7) / 8) * 8 * (unsigned)ng), block(kWave);
-  if (!HAS_RENDER || (a.imH == a.R && a.imW == a.C))
-    hipLaunchKernelGGL((sg_bwd_pk_kernel<1, HAS_GENV, HAS_RENDER, EW, HEADS>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((sg_bwd_pk_kernel<2, HAS_GENV, HAS_RENDER, EW, HEADS>), grid, block, 0, st, a);
+  with_pool(!HAS_RENDER || pool1(a), [&](auto P) {
+    hipLaunchKernelGGL((sg_bwd_pk_kernel<P(), HAS_GENV, HAS_RENDER, EW, HEADS>), grid, block, 0, st, a);
+  });
   return (int)hipGetLastError();
 }
 template <bool HAS_GENV, bool HAS_RENDER>
 static int sgbwd_pk_launch(const Args& a, hipStream_t st) {
-  if constexpr (HAS_RENDER) {      // premap == 3: the same kernels built with the decoder heads as prologue / epilogue (bwd_heads_ok holds)
+  if constexpr (HAS_RENDER) {      // premap == 3: the same kernels built with the decoder heads as prologue / epilogue (heads_ok holds)
     if (a.premap == 3)
       return a.ew == 16 ? sgbwd_pk_launch_ew<HAS_GENV, HAS_RENDER, 16, true>(a, st) : sgbwd_pk_launch_ew<HAS_GENV, HAS_RENDER, 32, true>(a, st);
   }
@@ -229,26 +229,7 @@ static int sgbwd_launch(const Args& a, hipStream_t st) {
   // the reference's direction grids (16- and 32-wide): the packed half-wave kernel for every SGNum -- six lobes per half-wave,
   // one workgroup per 32 pixels and group of 12 lobes (SGNum <= 6 leaves the upper half's lobe slots empty)
   if (fast_ok(a) && !sgr_generic_forced()) return sgbwd_pk_launch<HAS_GENV, HAS_RENDER>(a, st);
-  if (!HAS_RENDER || (a.imH == a.R && a.imW == a.C)) return sgbwd_launch_k<1, HAS_GENV, HAS_RENDER>(a, st);
-  return sgbwd_launch_k<2, HAS_GENV, HAS_RENDER>(a, st);
-}
-
-// premap == 3: see fwd_heads_ok (sgr_forward.inl)
-static inline bool bwd_heads_ok(const Args& a) {
-  return fast_ok(a) && !sgr_generic_forced() && a.K > 6 && a.K <= 24;
-}
-
-static inline int check_pool_b(int R, int C, int imH, int imW, const char* who) {
-  const bool ok = (imH == R && imW == C) || (imH == 2 * R && imW == 2 * C);
-  SGR_SUPPORTED(ok, who);
-  return SGR_OK;
-}
-
-static inline void set_dims_b(Args& a, int bn, int K, int R, int C, int eh, int ew, int imH, int imW) {
-  a.bn = bn; a.K = K; a.R = R; a.C = C; a.J = eh * ew; a.Jpad = sgr_dirs_padded(a.J); a.imH = imH; a.imW = imW;
-  a.eh = eh; a.ew = ew;
-  a.rows = reinterpret_cast<const float*>(a.dirs) + 4 * (size_t)a.Jpad;
-  a.cols = a.rows + 8 * (size_t)((eh + 1) / 2 * 2);
+  return with_pool(!HAS_RENDER || pool1(a), [&](auto P) { return sgbwd_launch_k<P(), HAS_GENV, HAS_RENDER>(a, st); });
 }
 
 }  // namespace sgr

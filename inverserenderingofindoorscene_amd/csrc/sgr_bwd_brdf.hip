@@ -4,7 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "sgr_pk.inl"
-#include "sgr_launch.h"
+#include "sgr_layer_launch.h"
 
 #ifndef SGR_TJ
 #define SGR_TJ 32
@@ -398,12 +398,12 @@ static int brdf_launch_vec(const Args& a, hipStream_t st) {
 
 template <int POOL>
 static int brdf_launch(const Args& a, hipStream_t st) {
-  if (a.K == 0 && a.ew == 16 && 3LL * a.R * a.C * a.J * 4 < (1LL << 31) && !sgr_generic_forced()) {
-    hipLaunchKernelGGL((brdf_bwd_pk_half_kernel<POOL>), dim3((unsigned)(a.bn * ((a.R * a.C + kPx - 1) / kPx))), dim3(kWave), 0, st, a);
+  if (a.K == 0 && a.ew == 16 && fast_ok(a) && !sgr_generic_forced()) {
+    hipLaunchKernelGGL((brdf_bwd_pk_half_kernel<POOL>), half_wave_grid(a.bn, a.R, a.C), dim3(kWave), 0, st, a);
     return (int)hipGetLastError();
   }
   if (a.K > 0 && a.K <= 12 && a.ew == 16 && !sgr_generic_forced()) {
-    const dim3 grid((unsigned)(a.bn * ((a.R * a.C + kPx - 1) / kPx))), block(kWave);
+    const dim3 grid = half_wave_grid(a.bn, a.R, a.C), block(kWave);
     if (a.K <= 6) hipLaunchKernelGGL((brdf_bwd_pk_sg_kernel<POOL, 6>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((brdf_bwd_pk_sg_kernel<POOL, 12>), grid, block, 0, st, a);
     return (int)hipGetLastError();
@@ -429,18 +429,15 @@ extern "C" int sgr_render_bwd_brdf(const float* g_diffuse, const float* g_spec, 
   SGR_REQUIRE(env || (axis && lamb && weight && K > 0), "sgr_render_bwd_brdf: need either env or the SG parameters");
   SGR_REQUIRE(bn > 0 && R > 0 && C > 0 && eh > 0 && ew > 0, "sgr_render_bwd_brdf: non-positive size");
   SGR_SUPPORTED(K <= SGR_MAX_LOBES, "sgr_render_bwd_brdf: SGNum > 32 is not supported");
-  const bool ok = (imH == R && imW == C) || (imH == 2 * R && imW == 2 * C);
-  SGR_SUPPORTED(ok, "sgr_render_bwd_brdf: BRDF-map / env-grid ratio must be 1 or 2 (pool first)");
+  if (int rc = check_pool(R, C, imH, imW, "sgr_render_bwd_brdf: BRDF-map / env-grid ratio must be 1 or 2 (pool first)")) return rc;
   Args a{};
   a.g_diffuse = g_diffuse; a.g_spec = g_spec; a.albedo = albedo; a.normal = normal; a.rough = rough;
   a.env_in = env; a.axis = axis; a.lamb = lamb; a.weight = weight;
   a.dirs = reinterpret_cast<const float4*>(dirs); a.view = view;
   a.g_albedo = g_albedo; a.g_normal = g_normal; a.g_rough = g_rough;
-  a.bn = bn; a.K = env ? 0 : K; a.R = R; a.C = C; a.J = eh * ew; a.Jpad = sgr_dirs_padded(a.J); a.imH = imH; a.imW = imW;
-  a.rows = reinterpret_cast<const float*>(a.dirs) + 4 * (size_t)a.Jpad;      // separable form of the table (include/sgrender.h)
-  a.cols = a.rows + 8 * (size_t)((eh + 1) / 2 * 2);
+  layer_dims(a, bn, env ? 0 : K, R, C, eh, ew, imH, imW);
   SGR_REQUIRE(premap >= 0 && premap <= 2, "sgr_render_bwd_brdf: premap must be 0, 1 or 2");
-  a.F0 = F0; a.premap = premap == 1 ? 1 : 0; a.eh = eh; a.ew = ew;      // 2 = post-tan SG inputs: nothing to pre-map, no SG chain rule here
+  a.F0 = F0; a.premap = premap == 1 ? 1 : 0;      // 2 = post-tan SG inputs: nothing to pre-map, no SG chain rule here
   const hipStream_t st = (hipStream_t)stream;
-  return sgr_check(imH == R ? brdf_launch<1>(a, st) : brdf_launch<2>(a, st), "sgr_render_bwd_brdf");
+  return sgr_check(with_pool(pool1(a), [&](auto P) { return brdf_launch<P()>(a, st); }), "sgr_render_bwd_brdf");
 }

@@ -11,7 +11,7 @@ extern "C" int sgr_sg_to_env_bwd(const float* g_env, const float* axis, const fl
   Args a{};
   a.g_env = g_env; a.axis = axis; a.lamb = lamb; a.weight = weight; a.dirs = reinterpret_cast<const float4*>(dirs);
   a.g_axis = g_axis; a.g_lamb = g_lamb; a.g_weight = g_weight;
-  set_dims_b(a, bn, K, R, C, eh, ew, R, C);
+  layer_dims(a, bn, K, R, C, eh, ew, R, C);
   a.premap = premap;
   return sgr_check(sgbwd_launch<true, false>(a, (hipStream_t)stream), "sgr_sg_to_env_bwd");
 }

@@ -6,6 +6,7 @@
 #include "sgr_launch.h"
 #include <string.h>
 #include "sgr_pk.inl"
+#include "sgr_layer_launch.h"
 
 #ifndef SGR_TJ
 #define SGR_TJ 32
@@ -151,20 +152,18 @@ static int fwd_launch_k(const Args& a, hipStream_t st) {
 template <int KP, bool WRITE_ENV, bool DO_RENDER, bool HEADS = false>
 static int fwd_pk_launch(const Args& a, hipStream_t st) {
   const dim3 grid = wave_grid(a.bn, a.R, a.C), block(kWave);
-  if (!DO_RENDER || (a.imH == a.R && a.imW == a.C))
-    hipLaunchKernelGGL((fwd_pk_kernel<KP, 1, WRITE_ENV, DO_RENDER, false, HEADS>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((fwd_pk_kernel<KP, 2, WRITE_ENV, DO_RENDER, false, HEADS>), grid, block, 0, st, a);
+  with_pool(!DO_RENDER || pool1(a), [&](auto P) {
+    hipLaunchKernelGGL((fwd_pk_kernel<KP, P(), WRITE_ENV, DO_RENDER, false, HEADS>), grid, block, 0, st, a);
+  });
   return (int)hipGetLastError();
 }
 // packed half-wave forward: 32 pixels x 2 groups of KPW lobes per wave, OCC resident waves per SIMD, RPF table rows per env flush
 template <bool WRITE_ENV, bool DO_RENDER, int OCC, int KPW, int EW, int RPF, bool HEADS>
 static int fwd_pk_half_launch(const Args& a, hipStream_t st) {
-  const dim3 grid((unsigned)(a.bn * ((a.R * a.C + kPx - 1) / kPx))), block(kWave);
-  if (!DO_RENDER || (a.imH == a.R && a.imW == a.C))
-    hipLaunchKernelGGL((fwd_pk_half_kernel<1, WRITE_ENV, DO_RENDER, OCC, KPW, EW, RPF, HEADS>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((fwd_pk_half_kernel<2, WRITE_ENV, DO_RENDER, OCC, KPW, EW, RPF, HEADS>), grid, block, 0, st, a);
+  const dim3 grid = half_wave_grid(a.bn, a.R, a.C), block(kWave);
+  with_pool(!DO_RENDER || pool1(a), [&](auto P) {
+    hipLaunchKernelGGL((fwd_pk_half_kernel<P(), WRITE_ENV, DO_RENDER, OCC, KPW, EW, RPF, HEADS>), grid, block, 0, st, a);
+  });
   return (int)hipGetLastError();
 }
 // Which packed kernel runs which shape.  Every choice is a measured one (the A/B records are
@@ -191,7 +190,7 @@ static int fwd_fast_launch_h(const Args& a, hipStream_t st) {
 }
 template <bool WRITE_ENV, bool DO_RENDER>
 static int fwd_fast_launch(const Args& a, hipStream_t st) {
-  if constexpr (DO_RENDER) {      // premap == 3 (decoder heads as the prologue; fwd_heads_ok holds): the same kernels built with HEADS
+  if constexpr (DO_RENDER) {      // premap == 3 (decoder heads as the prologue; heads_ok holds): the same kernels built with HEADS
     if (a.premap == 3) return fwd_fast_launch_h<WRITE_ENV, DO_RENDER, true>(a, st);
   }
   return fwd_fast_launch_h<WRITE_ENV, DO_RENDER, false>(a, st);
@@ -200,15 +199,10 @@ static int fwd_fast_launch(const Args& a, hipStream_t st) {
 // forwardEnv alone (env image given): the packed half-wave kernel of sgr_pk.inl (round 4; round 1's scalar one-pixel-per-lane kernel
 // with its 24 KB of LDS per wave measured 110 us against 105 warm, 160 against 158 cold -- profiles/r04c_kbench.txt -- and is gone)
 static int render_fast_launch(const Args& a, hipStream_t st) {
-  const bool p1 = (a.imH == a.R && a.imW == a.C);
-  const dim3 grid((unsigned)(a.bn * ((a.R * a.C + kPx - 1) / kPx))), block(kWave);
-  if (a.ew == 16) {
-    if (p1) hipLaunchKernelGGL((render_pk_half_kernel<1, 16>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((render_pk_half_kernel<2, 16>), grid, block, 0, st, a);
-  } else {
-    if (p1) hipLaunchKernelGGL((render_pk_half_kernel<1, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((render_pk_half_kernel<2, 32>), grid, block, 0, st, a);
-  }
+  const dim3 grid = half_wave_grid(a.bn, a.R, a.C), block(kWave);
+  with_ew(a.ew, [&](auto E) {
+    with_pool(pool1(a), [&](auto P) { hipLaunchKernelGGL((render_pk_half_kernel<P(), E()>), grid, block, 0, st, a); });
+  });
   return (int)hipGetLastError();
 }
 
@@ -216,27 +210,7 @@ template <bool FROM_SG, bool WRITE_ENV, bool DO_RENDER>
 static int fwd_launch(const Args& a, hipStream_t st) {
   if (!FROM_SG && DO_RENDER && fast_ok(a) && !sgr_generic_forced()) return render_fast_launch(a, st);
   if (FROM_SG && fast_ok(a) && a.K <= 24 && !sgr_generic_forced()) return fwd_fast_launch<WRITE_ENV, DO_RENDER>(a, st);
-  if (!DO_RENDER || (a.imH == a.R && a.imW == a.C)) return fwd_launch_k<1, FROM_SG, WRITE_ENV, DO_RENDER>(a, st);
-  return fwd_launch_k<2, FROM_SG, WRITE_ENV, DO_RENDER>(a, st);
-}
-
-// premap == 3 (the decoder heads as a prologue) is implemented in the packed kernels' lobe loader (sgr_pk.inl) only: the shapes
-// the default dispatch above sends there
-static inline bool fwd_heads_ok(const Args& a) {
-  return fast_ok(a) && !sgr_generic_forced() && a.K > 6 && a.K <= 24;
-}
-
-static inline int check_pool(int R, int C, int imH, int imW, const char* who) {
-  const bool ok = (imH == R && imW == C) || (imH == 2 * R && imW == 2 * C);
-  SGR_SUPPORTED(ok, who);
-  return SGR_OK;
-}
-
-static inline void set_dims(Args& a, int bn, int K, int R, int C, int eh, int ew, int imH, int imW) {
-  a.bn = bn; a.K = K; a.R = R; a.C = C; a.J = eh * ew; a.Jpad = sgr_dirs_padded(a.J); a.imH = imH; a.imW = imW;
-  a.eh = eh; a.ew = ew;
-  a.rows = reinterpret_cast<const float*>(a.dirs) + 4 * (size_t)a.Jpad;
-  a.cols = a.rows + 8 * (size_t)((eh + 1) / 2 * 2);
+  return with_pool(!DO_RENDER || pool1(a), [&](auto P) { return fwd_launch_k<P(), FROM_SG, WRITE_ENV, DO_RENDER>(a, st); });
 }
 
 }  // namespace sgr

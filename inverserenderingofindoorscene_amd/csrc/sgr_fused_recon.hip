@@ -477,18 +477,14 @@ using namespace sgr;
 
 static int recon_tiles(int RC) { return (RC + kWave - 1) / kWave; }
 // fused objective kernels: 8x16-style (envWidth 16) and 16x32-style (envWidth 32) grids, up to 24 lobes
-static bool fused_recon_ok(int K, int R, int C, int eh, int ew) {
-  const long long env_bytes = 3LL * R * C * eh * ew * 4;
-  return (ew == 16 || ew == 32) && K <= 24 && K >= 1 && env_bytes < (1LL << 31);
-}
+static bool fused_recon_ok(int K, int R, int C, int eh, int ew) { return fast_ok(R, C, eh, ew) && K <= 24 && K >= 1; }
 
 extern "C" int sgr_fused_recon_supported(int K, int R, int C, int eh, int ew) { return fused_recon_ok(K, R, C, eh, ew) ? 1 : 0; }
 
-static int recon_tiles32(int RC) { return (RC + kPx - 1) / kPx; }
 static int recon_tiles16(int RC) { return (RC + 15) / 16; }
 // workspace: [bn] per-image mask sums | [4] scale | [bn,tiles32,3] forward partials | [bn,tiles16] loss partials
 extern "C" int sgr_fused_recon_workspace_floats(int bn, int R, int C) {
-  return bn + 4 + bn * recon_tiles32(R * C) * 3 + bn * recon_tiles16(R * C);
+  return bn + 4 + bn * half_wave_tiles(R, C) * 3 + bn * recon_tiles16(R * C);
 }
 
 static int fused_fwd_recon_impl(const float* albedo, const float* normal, const float* rough, const float* axis, const float* lamb,
@@ -508,7 +504,7 @@ static int fused_fwd_recon_impl(const float* albedo, const float* normal, const 
   a.dirs = reinterpret_cast<const float4*>(dirs); a.view = view; a.diffuse = diffuse; a.spec = spec;
   a.env_gt = env_gt; a.seg_small = seg_small; a.seg_pool2 = seg_pool2; a.env_ind = env_ind; a.mask = mask;
   a.lamb_tan = lamb_tan; a.weight_tan = weight_tan;
-  set_dims(a, bn, K, R, C, eh, ew, imH, imW);
+  layer_dims(a, bn, K, R, C, eh, ew, imH, imW);
   a.F0 = F0; a.premap = premap == 1 ? 1 : (premap == 3 ? 3 : 0);
   SGR_REQUIRE(premap >= 0 && premap <= 3, "sgr_fused_fwd_recon: premap must be 0..3");
   SGR_SUPPORTED(premap != 3 || K > 6, "sgr_fused_fwd_recon: premap 3 (decoder heads as a prologue) needs 6 < SGNum <= 24");
@@ -519,34 +515,27 @@ static int fused_fwd_recon_impl(const float* albedo, const float* normal, const 
   // (profiles/r05c_bench_ab.txt): objective step 0.500-0.513 vs 0.503-0.504 ms, with standalone heads 0.776 vs 0.781-0.782 -- a tie on warm
   // data, at 1.04-1.1x the algorithmic traffic instead of 1.46x, so the instantiation is gone.  Up to six lobes: one pixel per lane.
   const bool wide = K > 6 || ew == 32;
-  const int tiles = wide ? recon_tiles32(R * C) : recon_tiles(R * C);
+  const int tiles = wide ? half_wave_tiles(R, C) : recon_tiles(R * C);
   float* den_img = workspace;
   float* ws0 = workspace + bn + 4;
   a.ws = ws0;
   const hipStream_t st = (hipStream_t)stream;
-  const bool p1 = (imH == R && imW == C);
-  const bool heads = premap == 3;
   if (wide) {
-    const dim3 grid((unsigned)(bn * tiles)), block(kWave);
-#define SGR_LAUNCH_GT(KPW_, EW_, OCC_)                                                                        \
-    do {                                                                                                      \
-      if (heads) {                                                                                            \
-        if (p1) hipLaunchKernelGGL((fwd_pk_half_gt_kernel<1, KPW_, EW_, OCC_, true>), grid, block, 0, st, a);  \
-        else hipLaunchKernelGGL((fwd_pk_half_gt_kernel<2, KPW_, EW_, OCC_, true>), grid, block, 0, st, a);     \
-      } else {                                                                                                \
-        if (p1) hipLaunchKernelGGL((fwd_pk_half_gt_kernel<1, KPW_, EW_, OCC_>), grid, block, 0, st, a);        \
-        else hipLaunchKernelGGL((fwd_pk_half_gt_kernel<2, KPW_, EW_, OCC_>), grid, block, 0, st, a);           \
-      }                                                                                                       \
-    } while (0)
-    if (K <= 12 && ew == 16) SGR_LAUNCH_GT(6, 16, 3);
-    else if (K <= 12) SGR_LAUNCH_GT(6, 32, 2);
-    else if (ew == 16) SGR_LAUNCH_GT(12, 16, 2);
-    else SGR_LAUNCH_GT(12, 32, 2);
-#undef SGR_LAUNCH_GT
+    const dim3 grid = half_wave_grid(bn, R, C), block(kWave);
+    const auto launch = [&](auto KPW, auto E, auto OCC) {      // lobes per half-wave, envWidth, resident waves per SIMD
+      with_pool(pool1(a), [&](auto P) {
+        with_flag(premap == 3, [&](auto HEADS) {
+          hipLaunchKernelGGL((fwd_pk_half_gt_kernel<P(), KPW(), E(), OCC(), HEADS()>), grid, block, 0, st, a);
+        });
+      });
+    };
+    if (K <= 12 && ew == 16) launch(Int<6>{}, Int<16>{}, Int<3>{});
+    else if (K <= 12) launch(Int<6>{}, Int<32>{}, Int<2>{});
+    else if (ew == 16) launch(Int<12>{}, Int<16>{}, Int<2>{});
+    else launch(Int<12>{}, Int<32>{}, Int<2>{});
   } else {
     const dim3 grid = wave_grid(bn, R, C), block(kWave);
-    if (p1) hipLaunchKernelGGL((fwd_pk_kernel<6, 1, false, true, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((fwd_pk_kernel<6, 2, false, true, true>), grid, block, 0, st, a);
+    with_pool(pool1(a), [&](auto P) { hipLaunchKernelGGL((fwd_pk_kernel<6, P(), false, true, true>), grid, block, 0, st, a); });
   }
   if (deferred) {
     *deferred = FoldJob{ws0, coef, den_img, tiles};
@@ -584,9 +573,8 @@ extern "C" int sgr_fused_fwd_recon_seg(const float* albedo, const float* normal,
                                        float* weight_tan, float* diffuse, float* spec, float* mask, float* coef, float* parts,
                                        float* workspace, int bn, int K, int R, int C, int eh, int ew, int imH, int imW, float F0,
                                        int premap, void* stream) {
-  const bool same = segH == R && segW == C, twice = segH == 2 * R && segW == 2 * C;
-  SGR_SUPPORTED(same || twice, "sgr_fused_fwd_recon_seg: object mask / env-grid ratio must be 1 or 2 (pool first)");
-  return fused_fwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, seg, twice ? 1 : 0, env_ind, lamb_tan, weight_tan,
+  if (int rc = check_pool(R, C, segH, segW, "sgr_fused_fwd_recon_seg: object mask / env-grid ratio must be 1 or 2 (pool first)")) return rc;
+  return fused_fwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, seg, pool1(R, C, segH, segW) ? 0 : 1, env_ind, lamb_tan, weight_tan,
                               diffuse, spec, mask, coef, parts, workspace, bn, K, R, C, eh, ew, imH, imW, F0, premap, stream);
 }
 
@@ -604,10 +592,9 @@ extern "C" int sgr_light_objective_fwd(const float* albedo, const float* normal,
   SGR_REQUIRE(im && seg && im_small && seg_small && rendered && coef_ds && parts_r && render_err && scale_r && loss_workspace,
               "sgr_light_objective_fwd: NULL tensor");
   SGR_REQUIRE((g_diffuse == nullptr) == (g_spec == nullptr), "sgr_light_objective_fwd: g_diffuse / g_spec come together");
-  const bool same = imH == R && imW == C, twice = imH == 2 * R && imW == 2 * C;
-  SGR_SUPPORTED(same || twice, "sgr_light_objective_fwd: image / env-grid ratio must be 1 or 2 (pool first)");
+  if (int rc = check_pool(R, C, imH, imW, "sgr_light_objective_fwd: image / env-grid ratio must be 1 or 2 (pool first)")) return rc;
   FoldJob job{};
-  if (int rc = fused_fwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, seg, twice ? 1 : 0, env_ind, lamb_tan, weight_tan,
+  if (int rc = fused_fwd_recon_impl(albedo, normal, rough, axis, lamb, weight, dirs, view, env_gt, seg, pool1(R, C, imH, imW) ? 0 : 1, env_ind, lamb_tan, weight_tan,
                                     diffuse, spec, mask, coef_env, nullptr, recon_workspace, bn, K, R, C, eh, ew, brdfH, brdfW, F0, premap, stream, &job))
     return rc;
   return render_loss_fwd_launch(diffuse, spec, im, seg, im_small, seg_small, rendered, coef_ds, parts_r, render_err, scale_r, 3.0f, ren_weight,
@@ -635,9 +622,9 @@ static int fused_bwd_recon_impl(const float* albedo, const float* normal, const 
   a.dirs = reinterpret_cast<const float4*>(dirs); a.view = view; a.g_diffuse = g_diffuse; a.g_spec = g_spec;
   a.g_axis = g_axis; a.g_lamb = g_lamb; a.g_weight = g_weight;
   a.env_gt = env_gt; a.mask_in = mask; a.coef = coef; a.offset = offset;
-  set_dims(a, bn, K, R, C, eh, ew, imH, imW);
+  layer_dims(a, bn, K, R, C, eh, ew, imH, imW);
   a.F0 = F0; a.premap = premap;
-  const int tiles32 = recon_tiles32(R * C);
+  const int tiles32 = half_wave_tiles(R, C);
   // Round 5, measured and NOT adopted (profiles/r05a_objective_bwd_lane_groups_kbench.txt, r05a_sq_config2_batch16_objective_k12ng4.txt; one box,
   // three alternations): 7..12 lobes on the 8x16 grid as FOUR lane groups of THREE lobes (a quarter of the accumulators per lane; the
   // template parameters it needed are gone again).  Asked for three waves per SIMD: 168 VGPRs, 56 B of scratch outside the hot loop, 2.78 resident
@@ -652,27 +639,16 @@ static int fused_bwd_recon_impl(const float* albedo, const float* normal, const 
   a.ws = ws1; a.den_img = den_img; a.den_global = den_global; a.rec_w3j = rec_weight / (3.0f * (float)(eh * ew));
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(bn * tiles)), block(kWave);
-  const bool p1 = (imH == R && imW == C);
-  {
-#define SGR_LAUNCH_BR(EW_, NG_)                                                                              \
-    do {                                                                                                     \
-      if (!grads) {                                                                                          \
-        if (premap == 3) hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<1, EW_, NG_, true, false>), grid, block, 0, st, a);   \
-        else hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<1, EW_, NG_, false, false>), grid, block, 0, st, a);              \
-      } else if (premap == 3) {                                                                              \
-        if (p1) hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<1, EW_, NG_, true>), grid, block, 0, st, a);      \
-        else hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<2, EW_, NG_, true>), grid, block, 0, st, a);         \
-      } else {                                                                                               \
-        if (p1) hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<1, EW_, NG_>), grid, block, 0, st, a);            \
-        else hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<2, EW_, NG_>), grid, block, 0, st, a);               \
-      }                                                                                                      \
-    } while (0)
-    if (!four && ew == 16) SGR_LAUNCH_BR(16, 2);
-    else if (!four) SGR_LAUNCH_BR(32, 2);
-    else if (ew == 16) SGR_LAUNCH_BR(16, 4);
-    else SGR_LAUNCH_BR(32, 4);
-#undef SGR_LAUNCH_BR
-  }
+  with_ew(ew, [&](auto E) {
+    with_flag(four, [&](auto FOUR) {
+      constexpr int NG = FOUR() ? 4 : 2;      // lane groups per pixel
+      with_flag(premap == 3, [&](auto HEADS) {
+        // the loss value alone reads no BRDF map: one instantiation (POOL 1) serves both map sizes
+        if (!grads) hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<1, E(), NG, HEADS(), false>), grid, block, 0, st, a);
+        else with_pool(pool1(a), [&](auto P) { hipLaunchKernelGGL((sg_bwd_recon_pk_kernel<P(), E(), NG, HEADS()>), grid, block, 0, st, a); });
+      });
+    });
+  });
   hipLaunchKernelGGL(recon_fold1, dim3(1), dim3(kFold1Threads), 0, st, ws1, den_img, parts, bn, tiles, tail);     // parts = (loss numerator, local sum of the env mask)
   return sgr_check((int)hipGetLastError(), "sgr_fused_bwd_recon");
 }

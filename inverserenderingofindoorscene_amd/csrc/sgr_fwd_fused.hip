@@ -14,10 +14,10 @@ static int fused_fwd_impl(const char* who, const float* albedo, const float* nor
   a.albedo = albedo; a.normal = normal; a.rough = rough; a.axis = axis; a.lamb = lamb; a.weight = weight;
   a.dirs = reinterpret_cast<const float4*>(dirs); a.view = view; a.env_out = env; a.diffuse = diffuse; a.spec = spec;
   a.lamb_tan = lamb_tan; a.weight_tan = weight_tan;
-  set_dims(a, bn, K, R, C, eh, ew, imH, imW);
+  layer_dims(a, bn, K, R, C, eh, ew, imH, imW);
   a.F0 = F0; a.premap = premap == 1 ? 1 : (premap == 3 ? 3 : 0);      // 2 (post-tan inputs, a backward-only distinction) is 0 here
   SGR_REQUIRE(premap >= 0 && premap <= 3, "sgr_fused_fwd: premap must be 0..3");
-  SGR_SUPPORTED(premap != 3 || fwd_heads_ok(a), "sgr_fused_fwd: premap 3 (decoder heads as a prologue) needs envWidth 16 or 32 and 6 < SGNum <= 24 (sgr_heads_prologue_supported)");
+  SGR_SUPPORTED(premap != 3 || heads_ok(a), "sgr_fused_fwd: premap 3 (decoder heads as a prologue) needs envWidth 16 or 32 and 6 < SGNum <= 24 (sgr_heads_prologue_supported)");
   const hipStream_t st = (hipStream_t)stream;
   return sgr_check(env ? fwd_launch<true, true, true>(a, st) : fwd_launch<true, false, true>(a, st), who);
 }
@@ -52,6 +52,6 @@ extern "C" int sgr_debug_trace_fwd(void* device_buffer) {
 // the prologue of the fused kernels and their chain rule as the epilogue of the backward kernels) is available for a configuration
 extern "C" int sgr_heads_prologue_supported(int K, int R, int C, int eh, int ew) {
   Args a{};
-  set_dims(a, 1, K, R, C, eh, ew, R, C);
-  return (K > 0 && R > 0 && C > 0 && eh > 0 && ew > 0 && fwd_heads_ok(a)) ? 1 : 0;
+  layer_dims(a, 1, K, R, C, eh, ew, R, C);
+  return (K > 0 && R > 0 && C > 0 && eh > 0 && ew > 0 && heads_ok(a)) ? 1 : 0;
 }

@@ -11,7 +11,7 @@ extern "C" int sgr_render_env_fwd(const float* albedo, const float* normal, cons
   Args a{};
   a.albedo = albedo; a.normal = normal; a.rough = rough; a.env_in = env;
   a.dirs = reinterpret_cast<const float4*>(dirs); a.view = view; a.diffuse = diffuse; a.spec = spec;
-  set_dims(a, bn, 0, R, C, eh, ew, imH, imW);
+  layer_dims(a, bn, 0, R, C, eh, ew, imH, imW);
   a.F0 = F0;
   return sgr_check(fwd_launch<false, false, true>(a, (hipStream_t)stream), "sgr_render_env_fwd");
 }

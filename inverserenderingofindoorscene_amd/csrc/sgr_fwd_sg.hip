@@ -12,7 +12,7 @@ extern "C" int sgr_sg_to_env_fwd(const float* axis, const float* lamb, const flo
   Args a{};
   a.axis = axis; a.lamb = lamb; a.weight = weight; a.dirs = reinterpret_cast<const float4*>(dirs);
   a.env_out = env; a.lamb_tan = lamb_tan; a.weight_tan = weight_tan;
-  set_dims(a, bn, K, R, C, eh, ew, R, C);
+  layer_dims(a, bn, K, R, C, eh, ew, R, C);
   a.premap = premap == 1 ? 1 : 0;
   return sgr_check(fwd_launch<true, true, false>(a, (hipStream_t)stream), "sgr_sg_to_env_fwd");
 }
@@ -26,16 +26,13 @@ extern "C" int sgr_sg_shading(const float* axis, const float* lamb, const float*
   SGR_REQUIRE(premap >= 0 && premap <= 2, "sgr_sg_shading: premap must be 0, 1 or 2");
   Args a{};
   a.axis = axis; a.lamb = lamb; a.weight = weight; a.dirs = reinterpret_cast<const float4*>(dirs); a.diffuse = shading;
-  set_dims(a, bn, K, R, C, eh, ew, R, C);
+  layer_dims(a, bn, K, R, C, eh, ew, R, C);
   a.premap = premap == 1 ? 1 : 0;
   const dim3 grid = wave_grid(bn, R, C), block(kWave);
   const hipStream_t st = (hipStream_t)stream;
-  if (ew == 16) {
-    if (K <= 12) hipLaunchKernelGGL((shading_fast_kernel<12, 16>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((shading_fast_kernel<24, 16>), grid, block, 0, st, a);
-  } else {
-    if (K <= 12) hipLaunchKernelGGL((shading_fast_kernel<12, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((shading_fast_kernel<24, 32>), grid, block, 0, st, a);
-  }
+  with_ew(ew, [&](auto E) {
+    if (K <= 12) hipLaunchKernelGGL((shading_fast_kernel<12, E()>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((shading_fast_kernel<24, E()>), grid, block, 0, st, a);
+  });
   return sgr_check((int)hipGetLastError(), "sgr_sg_shading");
 }

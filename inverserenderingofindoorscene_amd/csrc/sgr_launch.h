@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 
 #include "../../include/sgrender.h"
 
@@ -41,8 +42,31 @@ int render_loss_fwd_launch(const float* diffuse, const float* spec, const float*
   } while (0)
 
 // SGR_GENERIC=1 forces the table-driven generic kernels (tuning / test knob); read once per process
-#include <stdlib.h>
 static inline bool sgr_generic_forced() {
   static const bool on = [] { const char* e = getenv("SGR_GENERIC"); return e != nullptr && e[0] != 0 && !(e[0] == '0' && e[1] == 0); }();
   return on;
 }
+
+namespace sgr {
+// Where the parts of the direction table start, in floats (include/sgrender.h): [Jpad][4] (lx, ly, lz, omega) with J = eh * ew padded
+// to 32 | the separable rows [eh rounded up to even][8] | the separable columns, 8 * ew floats.  sgr_fill_direction_table (sgr_api.hip)
+// writes by it and layer_dims (sgr_layer_launch.h) points the kernels into it; the offsets INSIDE the column block (cols + ew,
+// cols + 4 * ew) belong to the kernels that read it (sgr_pk.inl) and to the writer's comments.
+struct DirLayout { int Jpad, rows, cols, floats; };
+static inline int dirs_padded(int J) { return (J + 31) / 32 * 32; }
+static inline DirLayout dir_layout(int eh, int ew) {
+  DirLayout t;
+  t.Jpad = dirs_padded(eh * ew);
+  t.rows = 4 * t.Jpad;
+  t.cols = t.rows + 8 * ((eh + 1) / 2 * 2);
+  t.floats = t.cols + 8 * ew;
+  return t;
+}
+
+// BRDF maps, image and object mask come at the env grid's size or at twice it (POOL = 1 | 2: the kernels average 2x2 on the fly)
+static inline bool pool1(int R, int C, int imH, int imW) { return imH == R && imW == C; }
+static inline int check_pool(int R, int C, int imH, int imW, const char* who) {
+  SGR_SUPPORTED(pool1(R, C, imH, imW) || (imH == 2 * R && imW == 2 * C), who);
+  return SGR_OK;
+}
+}  // namespace sgr

@@ -413,8 +413,7 @@ int sgr::render_loss_fwd_launch(const float* diffuse, const float* spec, const f
               "sgr_render_loss_fwd: NULL tensor");
   SGR_REQUIRE((loss == nullptr) == (scale == nullptr) && (!loss || divisor > 0.0f), "sgr_render_loss_fwd: loss / scale / divisor");
   SGR_REQUIRE(bn > 0 && R > 0 && C > 0, "sgr_render_loss_fwd: non-positive size");
-  const bool ok = (imH == R && imW == C) || (imH == 2 * R && imW == 2 * C);
-  SGR_SUPPORTED(ok, "sgr_render_loss_fwd: image / env-grid ratio must be 1 or 2 (pool first)");
+  if (int rc = check_pool(R, C, imH, imW, "sgr_render_loss_fwd: image / env-grid ratio must be 1 or 2 (pool first)")) return rc;
   const hipStream_t st = (hipStream_t)stream;
   float* wsA = workspace;
   float* wsB = wsA + (size_t)bn * kSplitA * 6;
@@ -423,7 +422,7 @@ int sgr::render_loss_fwd_launch(const float* diffuse, const float* spec, const f
   const dim3 grid(kSplitBC, bn), block(kLossThreads);
   const int RC = R * C;
   const dim3 grid_a(kSplitA + (job.ws ? 1 : 0), bn);
-  if (imH == R)
+  if (pool1(R, C, imH, imW))
     hipLaunchKernelGGL((loss_stage_a<1>), grid_a, block, 0, st, diffuse, spec, im, seg, im_small, seg_small, wsA, ticket, R, C, imH, imW, job);
   else
     hipLaunchKernelGGL((loss_stage_a<2>), grid_a, block, 0, st, diffuse, spec, im, seg, im_small, seg_small, wsA, ticket, R, C, imH, imW, job);
