@@ -575,6 +575,35 @@ int sgr_gn_resize_bwd(const float* g, const float* x, const float* weight, const
                       float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
                       const long long* x_strides, void* stream);
 
+/* The statistics of sgr_gn_stage_fwd without its apply pass: stats [B,G,4] of x [B,C,H,W] (read through x_strides), the same bits
+ * sgr_gn_stage_fwd writes.  workspace: sgr_gn_stage_workspace_floats(B, C, G, H, W, 0, 0) floats, 8-byte aligned.  Two launches. */
+int sgr_gn_moments(const float* x, float* stats, float* workspace, int B, int C, int G, int H, int W, const long long* x_strides, float eps,
+                   void* stream);
+
+/* ---- The BRDF decoders' final step, x_orig = dconvFinal(dpadFinal(dx6)) (models.py:155-156, 187): ReplicationPad2d(1) followed by
+ * Conv2d(C -> 3, kernel 3, stride 1), without the padded copy.  Contract: DESIGN.md section 8g.  With cl(t, n) = min(max(t, 0), n - 1):
+ *   out[b,o,i,j] = bias[o] + sum_{c,kh,kw} weight[o,c,kh,kw] y[b,c,cl(i+kh-1,H),cl(j+kw-1,W)]
+ * x [B,C,H,W] is read through its element strides (x_strides: four long long, host memory, read during the call); weight [O,C,3,3],
+ * bias [O], out [B,O,H,W], the cotangent and the gradients are contiguous.  O must be 3 and C at most 256; anything else is refused with
+ * SGR_ERR_UNSUPPORTED and a message that names the composition to use.
+ * stats == NULL: y = x.  stats [B,G,4] (sgr_gn_moments or sgr_gn_stage_fwd) with gn_weight, gn_bias [C]: y = relu(group_norm(x)) is formed
+ * on load, with the bits sgr_gn_stage_fwd would have written, and never stored (G is ignored without stats).
+ * Forward: one launch, no workspace.  Backward: one launch for dy, two for dweight / dbias; no atomics, bit-identical runs, image b
+ * independent of the rest of the batch, the same bits for every layout of x. */
+
+/* Floats of workspace (owned by the caller) for sgr_final_conv_bwd's dweight / dbias.  Pure host function; 0 for sizes the entry points refuse. */
+long long sgr_final_conv_workspace_floats(int B, int C, int O, int H, int W);
+
+int sgr_final_conv_fwd(const float* x, const float* weight, const float* bias, const float* gn_weight, const float* gn_bias, const float* stats,
+                       float* out, int B, int C, int O, int G, int H, int W, const long long* x_strides, void* stream);
+
+/* g: the cotangent of out.  dy [B,C,H,W] is the gradient at y (with a prologue: at the ReLU's output, unmasked -- sgr_gn_stage_bwd with
+ * Cs == 0 masks it and carries it on to x); dweight [O,C,3,3], dbias [O].  A NULL one is not wanted and costs nothing: dy needs weight,
+ * dweight needs x (and, with stats, the GroupNorm parameters: y is recomputed, not read), dweight / dbias need the workspace. */
+int sgr_final_conv_bwd(const float* g, const float* x, const float* weight, const float* gn_weight, const float* gn_bias, const float* stats,
+                       float* dy, float* dweight, float* dbias, float* workspace, int B, int C, int O, int G, int H, int W,
+                       const long long* x_strides, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

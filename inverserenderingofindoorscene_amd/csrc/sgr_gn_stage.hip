@@ -114,6 +114,16 @@ __device__ __forceinline__ void gn_group_stat(const double* __restrict__ partial
   __syncthreads();
 }
 
+// the statistics alone (sgr_gn_moments): one wave per (b, g) does the fold the apply kernels do and writes what they write
+__global__ __launch_bounds__(64) void gn_stats_kernel(const double* __restrict__ partials, float* __restrict__ stats, int S, double n, float eps) {
+  __shared__ float sh[4];
+  gn_group_stat(partials, blockIdx.x, S, n, eps, sh);
+  if (threadIdx.x == 0) {
+    float* st = stats + 4 * (long long)blockIdx.x;
+    st[0] = sh[0]; st[1] = sh[1]; st[2] = sh[2]; st[3] = sh[3];
+  }
+}
+
 // plain form: y = relu(gn(x)); a thread takes runs of four plane elements
 template <bool VEC>
 __global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
@@ -865,4 +875,30 @@ extern "C" int sgr_gn_resize_bwd(const float* g, const float* x, const float* we
     }
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_bwd");
+}
+
+// ---- the statistics without the apply pass: what a consumer that normalises on load (sgr_final_conv_fwd) needs ------------------------------
+
+extern "C" int sgr_gn_moments(const float* x, float* stats, float* workspace, int B, int C, int G, int H, int W, const long long* x_strides, float eps,
+                              void* stream) {
+  SGR_REQUIRE(x && stats && workspace && x_strides, "sgr_gn_moments: NULL tensor");
+  const int Cs = 0;
+  GN_CHECK_SIZES("sgr_gn_moments");
+  SGR_REQUIRE(eps > 0.0f, "sgr_gn_moments: eps must be positive");
+  SGR_SUPPORTED(g_plane_fits(x_strides, H, W), "sgr_gn_moments: negative or out-of-range plane strides");
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_moments: the workspace must be 8-byte aligned");
+  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
+  const int cpg = C / G, HW = H * W;
+  const long long n = (long long)cpg * HW;
+  const int S = gn_slices(n);
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  // the launch of sgr_gn_stage_fwd: the same partials, and gn_group_stat folds them to the same bits
+  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
+  if (g_plane_vec(x, xs, H, W))
+    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  else
+    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, st, partials, stats, S, (double)n, eps);
+  return sgr_check((int)hipGetLastError(), "sgr_gn_moments");
 }

@@ -1,5 +1,5 @@
 // The reduction scheme and the 1-or-4 float vector access of the streaming operators (sgr_loss.hip, sgr_brdf_loss.hip, sgr_brdf_input.hip,
-// sgr_glue.hip, sgr_brdf_heads.hip, sgr_gn_stage.hip, sgr_recon.hip / sgr_recon_fold.h), one definition each:
+// sgr_glue.hip, sgr_brdf_heads.hip, sgr_gn_stage.hip, sgr_final_conv.hip, sgr_recon.hip / sgr_recon_fold.h), one definition each:
 //   fp32 per-thread partials -> wave ladder -> the four wave sums through LDS -> ONE partial per workgroup in a workspace -> folded in
 //   double, in a fixed order, by the consumer's prologue.  No float atomics, no host synchronisation.
 // Bit-identical runs and results that do not depend on the batch rest on the ORDER of the additions, so every function below states
