@@ -604,6 +604,26 @@ int sgr_final_conv_bwd(const float* g, const float* x, const float* weight, cons
                        float* dy, float* dweight, float* dbias, float* workspace, int B, int C, int O, int G, int H, int W,
                        const long long* x_strides, void* stream);
 
+/* ---- The light decoders' final pad + 3x3 convolution (csrc/sgr_light_final_conv.hip) --------------------------------
+ * out = Conv2d(C -> O, k = 3)(ReplicationPad2d(1)(y)) -- x_orig = dconvFinal(dpadFinal(dx6)) of models.decoderLight (models.py:297-302, 334).
+ * fp32; 1 <= O <= 48; C a multiple of 16 in 16..256; H, W >= 1, H * W < 2^26, B <= 65535.  y [B,C,H,W] is read through y_strides (4 element
+ * strides, non-negative in the plane); everything else is contiguous: weight [O,C,3,3], bias [O], out [B,O,H,W].  Anything else returns
+ * SGR_ERR_UNSUPPORTED and a message that names the composition to use, and launches nothing.
+ * The forward and the data gradient run on the fp32-input matrix instruction (exact fp32, a fixed k-ordered fmaf chain); the weight and
+ * bias gradients run on the vector ALU.  Forward: one launch, no workspace.  Backward: one launch for dy, two for dweight / dbias; no
+ * atomics, bit-identical runs, image b independent of the rest of the batch, the same bits for every layout of y. */
+
+/* Floats of workspace (owned by the caller) for sgr_light_final_conv_bwd's dweight / dbias.  Pure host function; 0 for sizes the entry points refuse. */
+long long sgr_light_final_conv_workspace_floats(int B, int C, int O, int H, int W);
+
+int sgr_light_final_conv_fwd(const float* y, const float* weight, const float* bias, float* out, int B, int C, int O, int H, int W,
+                             const long long* y_strides, void* stream);
+
+/* g: the cotangent of out.  dy [B,C,H,W], dweight [O,C,3,3], dbias [O].  A NULL one is not wanted and costs nothing: dy needs weight, dweight
+ * needs y, dweight / dbias need the workspace. */
+int sgr_light_final_conv_bwd(const float* g, const float* y, const float* weight, float* dy, float* dweight, float* dbias, float* workspace,
+                             int B, int C, int O, int H, int W, const long long* y_strides, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@
 
 When the reference's final resize to the image fires (``dx6``'s size differs from the image's, models.py:185-186), the resized map has to
 exist: compose ``group_norm_relu_resize(x, ..., size=im.shape[2:])`` and ``final_conv``.  ``decoderLight``'s final convolution (128 -> 12 /
-36 channels) is outside the domain and stays with PyTorch.  The heads stay ``brdf_heads``.  DESIGN.md section 8g states the arithmetic."""
+36 channels) is outside the domain: it is ``light_final_conv``.  The heads stay ``brdf_heads``.  DESIGN.md section 8g states the arithmetic."""
 from __future__ import annotations
 
 import torch
