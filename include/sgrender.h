@@ -624,6 +624,27 @@ int sgr_light_final_conv_fwd(const float* y, const float* weight, const float* b
 int sgr_light_final_conv_bwd(const float* g, const float* y, const float* weight, float* dy, float* dweight, float* dbias, float* workspace,
                              int B, int C, int O, int H, int W, const long long* y_strides, void* stream);
 
+/* ---- The encoders' pad + 4x4 stride-2 convolution (csrc/sgr_encoder_conv.hip) -------------------------------------------
+ * out = Conv2d(C -> O, k = 4, stride = 2)(pad(x)) with pad = ReplicationPad2d(1) (pad_mode 0) or ZeroPad2d(1) (pad_mode 1): encoder0.conv1 /
+ * conv2 and encoderLight.preProcess[1] / [5] / conv1 of models.py:93-115, 122-126, 213-246, 254-266.  fp32; 1 <= C <= 160; O a multiple of
+ * 16 in 16..128; H, W >= 2; Ho = H / 2, Wo = W / 2 (rounded down), Ho * Wo < 2^26; B <= 65535.  x [B,C,H,W] is read through x_strides (4
+ * element strides, non-negative in the plane); everything else is contiguous: weight [O,C,4,4], bias [O], out [B,O,Ho,Wo].  Anything else
+ * returns SGR_ERR_UNSUPPORTED and a message that names the composition to use (the deeper encoder layers stay F.pad + F.conv2d), and
+ * launches nothing.  The forward, the data gradient and the weight gradient run on the fp32-input matrix instruction (exact fp32, a fixed
+ * k-ordered fmaf chain); the bias gradient and, in replicate mode, the data gradient of the first and last row and column run on the vector
+ * ALU.  No atomics: bit-identical runs, image b independent of the rest of the batch, the same bits for every layout of x. */
+
+/* Floats of workspace (owned by the caller) for sgr_encoder_conv_bwd's dweight / dbias.  Pure host function; 0 for sizes the entry points refuse. */
+long long sgr_encoder_conv_workspace_floats(int B, int C, int O, int H, int W);
+
+int sgr_encoder_conv_fwd(const float* x, const float* weight, const float* bias, float* out, int B, int C, int O, int H, int W,
+                         const long long* x_strides, int pad_mode, void* stream);
+
+/* g: the cotangent of out.  dx [B,C,H,W], dweight [O,C,4,4], dbias [O].  A NULL one is not wanted and costs nothing: dx needs weight, dweight
+ * needs x, dweight / dbias need the workspace. */
+int sgr_encoder_conv_bwd(const float* g, const float* x, const float* weight, float* dx, float* dweight, float* dbias, float* workspace,
+                         int B, int C, int O, int H, int W, const long long* x_strides, int pad_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

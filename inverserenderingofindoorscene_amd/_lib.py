@@ -112,6 +112,9 @@ SIGNATURES = {
     "sgr_light_final_conv_workspace_floats": ([_I] * 5, c_longlong),
     "sgr_light_final_conv_fwd": ([_P] * 4 + [_I] * 5 + [_P, _P], c_int),
     "sgr_light_final_conv_bwd": ([_P] * 7 + [_I] * 5 + [_P, _P], c_int),
+    "sgr_encoder_conv_workspace_floats": ([_I] * 5, c_longlong),
+    "sgr_encoder_conv_fwd": ([_P] * 4 + [_I] * 5 + [_P, _I, _P], c_int),
+    "sgr_encoder_conv_bwd": ([_P] * 7 + [_I] * 5 + [_P, _I, _P], c_int),
 }
 
 _lib = None
