@@ -77,17 +77,33 @@ class Grid:
         return n * self.blur(n), n
 
 
-def pcg(matvec, b, x0, minv, rtol, maxiter):
-    """scipy.sparse.linalg.cg(A, b, x0, M=diag(minv), rtol=rtol, atol=0, maxiter=maxiter) for one right-hand side."""
+B_ZERO = -1      # pcg's record: the marker for a right-hand side of norm zero (no stop test is ever made)
+
+
+def pcg(matvec, b, x0, minv, rtol, maxiter, record=None):
+    """scipy.sparse.linalg.cg(A, b, x0, M=diag(minv), rtol=rtol, atol=0, maxiter=maxiter) for one right-hand side.
+
+    ``record``, if a dict, receives ``stop``: the iteration at whose top the solve stopped (0..maxiter-1), ``maxiter`` if it never
+    did, ``B_ZERO`` for ``|b| = 0``; and ``ratios``: ``|r| / atol`` at every stop test made, in order.  Recording reads the norm the
+    stop test computes anyway and changes no arithmetic."""
+    if record is not None:
+        record["stop"], record["ratios"] = int(maxiter), []
     bn = np.linalg.norm(b)
     if bn == 0:
+        if record is not None:
+            record["stop"] = B_ZERO
         return b.copy()
     atol = rtol * bn
     x = x0.copy()
     r = b - matvec(x) if x.any() else b.copy()
     rho_prev, p = None, None
     for it in range(int(maxiter)):
-        if np.linalg.norm(r) < atol:
+        rn = np.linalg.norm(r)
+        if record is not None:
+            record["ratios"].append(float(rn / atol))
+        if rn < atol:
+            if record is not None:
+                record["stop"] = it
             return x
         z = minv * r
         rho = np.dot(r, z)
@@ -98,6 +114,16 @@ def pcg(matvec, b, x0, minv, rtol, maxiter):
         r -= alpha * q
         rho_prev = rho
     return x
+
+
+def stop_margin(records):
+    """smallest |ln(|r| / atol)| over all stop tests of the recorded solves: how far the closest test was from going the other way
+    (inf if no test was made)"""
+    ratios = np.array([q for rec in records for q in rec["ratios"]], np.float64)
+    if ratios.size == 0:
+        return float("inf")
+    with np.errstate(divide="ignore"):
+        return float(np.abs(np.log(ratios)).min())
 
 
 class Solver:
@@ -116,45 +142,65 @@ class Solver:
         matvec = lambda y: diag * y - self.lam * self.n * g.nbr_sum(self.n * y)
         return ws, matvec, 1.0 / np.maximum(diag, self.amin)
 
-    def solve(self, pred, conf):
+    def _pcg_all(self, matvec, b, y0, minv, records):
+        cols = []
+        for c in range(b.shape[1]):
+            rec = None
+            if records is not None:
+                rec = {}
+                records.append(rec)
+            cols.append(pcg(matvec, b[:, c], y0[:, c], minv, self.tol, self.maxiter, rec))
+        return np.stack(cols, 1)
+
+    def solve(self, pred, conf, records=None):
         t = np.asarray(pred, np.float64).reshape(self.g.npixels, -1)
         w = np.asarray(conf, np.float64).reshape(-1)
         ws, matvec, minv = self._system(w)
         b = self.g.splat(t * w[:, None])
         y0 = b / np.maximum(ws, 1e-10)[:, None]
-        yhat = np.stack([pcg(matvec, b[:, c], y0[:, c], minv, self.tol, self.maxiter) for c in range(t.shape[1])], 1)
+        yhat = self._pcg_all(matvec, b, y0, minv, records)
         return self.g.slice(yhat), yhat
 
-    def solve_grad(self, grad, conf, yhat, pred):
+    def solve_grad(self, grad, conf, yhat, pred, records=None):
         gr = np.asarray(grad, np.float64).reshape(self.g.npixels, -1)
         t = np.asarray(pred, np.float64).reshape(self.g.npixels, -1)
         w = np.asarray(conf, np.float64).reshape(-1)
         ws, matvec, minv = self._system(w)
         b = self.g.splat(gr)
         y0 = b / self.g.splat(np.ones(self.g.npixels))[:, None]
-        yb = np.stack([pcg(matvec, b[:, c], y0[:, c], minv, self.tol, self.maxiter) for c in range(gr.shape[1])], 1)
+        yb = self._pcg_all(matvec, b, y0, minv, records)
         s = self.g.slice(yb)
         return s * w[:, None], (self.g.slice(-yb * yhat) + s * t).sum(1)
 
 
-def run_case(image, pred, conf, grad, params):
-    """One image through forward and backward.  ``params`` = (sigma_luma, sigma_chroma, sigma_spatial, lam, A_diag_min, cg_tol, cg_maxiter)."""
+def run_case(image, pred, conf, grad, params, record=True):
+    """One image through forward and backward.  ``params`` = (sigma_luma, sigma_chroma, sigma_spatial, lam, A_diag_min, cg_tol, cg_maxiter).
+
+    With ``record`` the result also has ``stops_fwd`` / ``stops_bwd`` (per channel: pcg's ``stop``) and ``margin`` (stop_margin over
+    both solves); the other entries have the same bits either way."""
     sl, sc, ss, lam, amin, tol, mi = params
     H, W = image.shape[:2]
     g = Grid(image, sl, sc, ss)
     s = Solver(g, lam, amin, tol, mi)
-    out, yhat = s.solve(pred, conf)
-    gp, gc = s.solve_grad(grad, conf, yhat, pred)
+    rf, rb = ([], []) if record else (None, None)
+    out, yhat = s.solve(pred, conf, rf)
+    gp, gc = s.solve_grad(grad, conf, yhat, pred, rb)
     C = out.shape[1]
-    return dict(idx=g.idx.reshape(H, W), nvertices=g.nvertices, m=s.m, n=s.n, yhat=yhat, out=out.reshape(H, W, C),
-                grad_pred=gp.reshape(H, W, C), grad_conf=gc.reshape(H, W))
+    res = dict(idx=g.idx.reshape(H, W), nvertices=g.nvertices, m=s.m, n=s.n, yhat=yhat, nbr=g.nbr, out=out.reshape(H, W, C),
+               grad_pred=gp.reshape(H, W, C), grad_conf=gc.reshape(H, W))
+    if record:
+        res.update(stops_fwd=np.array([r["stop"] for r in rf]), stops_bwd=np.array([r["stop"] for r in rb]), margin=stop_margin(rf + rb))
+    return res
 
 
 def run_batch(image, pred, conf, grad, params):
-    """NCHW batch wrapper: image [B,3,H,W], pred/grad [B,C,H,W], conf [B,1,H,W] -> dict of stacked NCHW fp64 results."""
+    """NCHW batch wrapper: image [B,3,H,W], pred/grad [B,C,H,W], conf [B,1,H,W] -> dict of stacked NCHW fp64 results; ``nbr`` and
+    ``yhat`` ([nvertices,10] and [nvertices,C] per image) as lists, ``stops_fwd`` / ``stops_bwd`` [B,C], ``margin`` over the batch."""
     outs = [run_case(np.moveaxis(image[b], 0, -1), np.moveaxis(pred[b], 0, -1), conf[b, 0], np.moveaxis(grad[b], 0, -1), params)
             for b in range(image.shape[0])]
     return dict(idx=np.stack([o["idx"] for o in outs]), nvertices=np.array([o["nvertices"] for o in outs]),
                 out=np.stack([np.moveaxis(o["out"], -1, 0) for o in outs]),
                 grad_pred=np.stack([np.moveaxis(o["grad_pred"], -1, 0) for o in outs]),
-                grad_conf=np.stack([o["grad_conf"] for o in outs])[:, None])
+                grad_conf=np.stack([o["grad_conf"] for o in outs])[:, None],
+                stops_fwd=np.stack([o["stops_fwd"] for o in outs]), stops_bwd=np.stack([o["stops_bwd"] for o in outs]),
+                margin=min(o["margin"] for o in outs), nbr=[o["nbr"] for o in outs], yhat=[o["yhat"] for o in outs])

@@ -55,6 +55,81 @@ def test_checker_reproduces_the_reference(name):
         assert np.all(z["nvertices"] < 0.9 * z["idx"].shape[1] * z["idx"].shape[2])
 
 
+_RECORDED = {}
+
+
+def recorded(name):
+    """every image of a fixture through the checker with the PCG record, once"""
+    if name not in _RECORDED:
+        z = load(name)
+        _RECORDED[name] = [BC.run_case(z["image"][b], z["pred"][b], z["conf"][b], z["grad"][b], tuple(z["params"])) for b in range(z["image"].shape[0])]
+    return _RECORDED[name]
+
+
+@pytest.mark.parametrize("name", SOLVER_CASES)
+def test_recording_the_pcg_changes_no_bit(name):
+    z = load(name)
+    for b, rec in enumerate(recorded(name)):
+        plain = BC.run_case(z["image"][b], z["pred"][b], z["conf"][b], z["grad"][b], tuple(z["params"]), record=False)
+        assert not {"stops_fwd", "stops_bwd", "margin"} & set(plain) and set(plain) | {"stops_fwd", "stops_bwd", "margin"} == set(rec)
+        for k, v in plain.items():
+            assert np.array_equal(v, rec[k]), (b, k)
+
+
+@pytest.mark.parametrize("name", SOLVER_CASES)
+def test_no_fixture_system_stops_in_mid_run(name):
+    """A recorded fact about the fixtures: with cg_tol = 1e-5 and 10 or 12 iterations every PCG either stops at iteration 0 (a constant
+    channel, or a start vector that already solves the system), has |b| = 0, or runs all its iterations -- the stop tests in between
+    never fire, by a margin of ln 2 at the least.  The one exception is m1wide, whose grid has no neighbour at all: its systems are
+    diagonal, the first step of a diagonally preconditioned CG solves them exactly, and its backward solves stop at iteration 1, all
+    channels together.  No fixture has channels of one image stopping at different iterations, or any stop after iteration 1.
+    tests/test_gpu_bilateral_edges.py makes the inputs that do."""
+    maxiter = int(load(name)["params"][6])
+    for b, rec in enumerate(recorded(name)):
+        stops = np.concatenate([rec["stops_fwd"], rec["stops_bwd"]])
+        print(f"{name}[{b}]: stops {stops.tolist()}  margin {rec['margin']:.3g}")
+        diagonal = bool(np.all(rec["nbr"] < 0))
+        assert diagonal == (name == "m1wide")
+        if diagonal:
+            assert np.all(rec["stops_fwd"] == 0) and np.all(rec["stops_bwd"] == 1), stops
+        else:
+            assert np.all((stops == 0) | (stops == BC.B_ZERO) | (stops == maxiter)), stops
+        assert rec["margin"] >= np.log(2.0)
+
+
+def test_pcg_record():
+    rng = np.random.default_rng(0)
+    q = np.linalg.qr(rng.standard_normal((6, 6)))[0]
+    A = q @ np.diag([1.0, 2.0, 3.0, 4.0, 5.0, 6.0]) @ q.T
+    b, x0, minv = rng.standard_normal(6), np.zeros(6), np.ones(6)
+    rec = {}
+    x = BC.pcg(lambda v: A @ v, b, x0, minv, 1e-8, 20, rec)
+    assert np.array_equal(x, BC.pcg(lambda v: A @ v, b, x0, minv, 1e-8, 20))
+    assert 1 <= rec["stop"] <= 7 and len(rec["ratios"]) == rec["stop"] + 1          # six distinct eigenvalues: done after six steps
+    assert all(r >= 1 for r in rec["ratios"][:-1]) and rec["ratios"][-1] < 1
+    assert np.linalg.norm(A @ x - b) < 1e-8 * np.linalg.norm(b) * 1.0001
+    assert BC.stop_margin([rec]) == min(abs(np.log(r)) for r in rec["ratios"])
+    BC.pcg(lambda v: A @ v, b, x0, minv, 1e-8, 3, rec)
+    assert rec["stop"] == 3 and len(rec["ratios"]) == 3                              # never stopped: maxiter
+    assert not BC.pcg(lambda v: A @ v, np.zeros(6), b, minv, 1e-8, 3, rec).any() and rec["stop"] == BC.B_ZERO and rec["ratios"] == []
+    assert BC.stop_margin([rec]) == float("inf")
+
+
+def test_cg_maxiter_0_returns_the_start_vector():
+    z = load("m0c3")
+    params = tuple(z["params"][:6]) + (0,)
+    image, pred, conf, grad = z["image"][0], z["pred"][0], z["conf"][0], z["grad"][0]
+    r = BC.run_case(image, pred, conf, grad, params)
+    g = BC.Grid(image, *params[:3])
+    w = conf.astype(np.float64).reshape(-1)
+    t = pred.astype(np.float64).reshape(g.npixels, -1)
+    y0 = g.splat(t * w[:, None]) / np.maximum(g.splat(w), 1e-10)[:, None]
+    assert np.array_equal(r["yhat"], y0) and np.array_equal(r["out"].reshape(g.npixels, -1), y0[g.idx])
+    yb0 = g.splat(grad.astype(np.float64).reshape(g.npixels, -1)) / g.splat(np.ones(g.npixels))[:, None]
+    assert np.array_equal(r["grad_pred"].reshape(g.npixels, -1), yb0[g.idx] * w[:, None])
+    assert np.all(r["stops_fwd"] == 0) and np.all(r["stops_bwd"] == 0) and r["margin"] == float("inf")
+
+
 def test_fixture_special_cases_are_what_they_claim():
     z = load("constch")
     assert np.all(z["pred"][..., 1] == z["pred"][0, 0, 0, 1]) and np.isfinite(z["out"]).all()
