@@ -556,6 +556,19 @@ int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const 
                      float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
                      void* stream);
 
+/* The same two with x, skip, out, the cotangent g, dx and dskip in bfloat16 (the 16 bits of an element as unsigned short; strides in
+ * elements); weight, bias, stats, dweight, dbias and the workspace (sgr_gn_stage_workspace_floats, the same sizes) stay fp32.  Contract
+ * (DESIGN.md section 8j): every bf16 result is the fp32 entry point's result on the upcast tensors, rounded once to bf16, round to nearest
+ * even, bit for bit; stats, dweight and dbias are the fp32 entry point's bits.  The same kernels instantiated on the element type: the same
+ * launches, sums in the same order, the same guarantees and the same refusals (with the fp32 entry points' messages). */
+int sgr_gn_stage_fwd_bf16(const unsigned short* x, const float* weight, const float* bias, const unsigned short* skip, unsigned short* out,
+                          float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
+                          const long long* skip_strides, float eps, void* stream);
+
+int sgr_gn_stage_bwd_bf16(const unsigned short* g, const unsigned short* x, const float* weight, const float* bias, const float* stats,
+                          unsigned short* dx, float* dweight, float* dbias, unsigned short* dskip, float* workspace, int B, int C, int G,
+                          int Cs, int H, int W, const long long* x_strides, void* stream);
+
 /* ---- The same stage with the reference's resize-to-skip branch taken (models.py:165-166, 170-171, 175-176, 180-181, 185-186; decoderLight:
  * 312-313 ... 332-333): y = relu(group_norm(x)) [B,C,H,W] is resized to Hs x Ws by interpolate(., [Hs, Ws], mode='bilinear') first.
  *   Cs == 0 (skip NULL):  out [B,C,Hs,Ws]       = the resized map                                   (the final stage)

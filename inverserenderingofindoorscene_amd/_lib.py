@@ -102,6 +102,8 @@ SIGNATURES = {
     "sgr_gn_stage_workspace_floats": ([_I] * 7, c_longlong),
     "sgr_gn_stage_fwd": ([_P] * 7 + [_I] * 6 + [_P, _P, _F, _P], c_int),
     "sgr_gn_stage_bwd": ([_P] * 10 + [_I] * 6 + [_P, _P], c_int),
+    "sgr_gn_stage_fwd_bf16": ([_P] * 7 + [_I] * 6 + [_P, _P, _F, _P], c_int),
+    "sgr_gn_stage_bwd_bf16": ([_P] * 10 + [_I] * 6 + [_P, _P], c_int),
     "sgr_gn_resize_workspace_floats": ([_I] * 9, c_longlong),
     "sgr_gn_resize_fwd": ([_P] * 7 + [_I] * 8 + [_P, _P, _F, _P], c_int),
     "sgr_gn_resize_bwd": ([_P] * 10 + [_I] * 8 + [_P, _P], c_int),

@@ -9,6 +9,33 @@
 
 namespace sgr {
 
+// ---- bf16 input / output: the kernels of the same-size stage are instantiated on the type of x, skip, the result,
+// the cotangent, dx and dskip; everything between a load and a store is the fp32 arithmetic below.  A bf16 element travels as its 16 bits.
+struct bf16 { unsigned short bits; };
+// upcast: the 16 bits become the upper half of the fp32 pattern -- exact, NaN and infinities included
+SGR_HD float bf16_up(unsigned short h) {
+  const unsigned u = (unsigned)h << 16;
+  float f;
+  __builtin_memcpy(&f, &u, 4);
+  return f;
+}
+// round to nearest, ties to even, on the bit pattern: the carry of the addition moves into the exponent where the mantissa overflows, up
+// to infinity from the largest finite values.  A NaN stays a NaN (quiet, sign and upper payload kept); infinities have a zero lower half
+// and pass through.
+SGR_HD unsigned short bf16_round(float f) {
+  unsigned u;
+  __builtin_memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+// what a kernel does with an element of its I/O type T (float or bf16) on load and on store
+SGR_HD float gn_in(float v) { return v; }
+SGR_HD float gn_in(bf16 v) { return bf16_up(v.bits); }
+template <typename T> SGR_HD T gn_out(float v);
+template <> SGR_HD float gn_out<float>(float v) { return v; }
+template <> SGR_HD bf16 gn_out<bf16>(float v) { return bf16{bf16_round(v)}; }
+
 // (mean, rstd) of a group from its two double-precision sums over n elements.  The mean is kept as an fp32 pair (mh + ml): at
 // x = 100 + N(0,1) an fp32 mean alone is off by up to 4e-6 of the standard deviation, in every element of the group alike.
 SGR_HD void gn_finish(double s, double ss, double n, float eps, float& mh, float& ml, float& rstd, float& var) {

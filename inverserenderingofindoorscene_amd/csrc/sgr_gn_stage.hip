@@ -18,6 +18,11 @@
 // x and skip are read through their strides (channels-last convolution outputs); every sum runs over logical indices, so the layout
 // changes no bit.  128-bit loads and stores where the layout and the alignment allow them, the same arithmetic element by element elsewhere.
 // The wave ladder of the sums (wave_sum), the 128-bit vector (Vec<4>) and its alignment test (aligned16) are sgr_reduce.h's.
+//
+// The kernels of the same-size forms are templates on the I/O type T of x, skip, the result, the cotangent, dx and dskip: float, or bf16
+// (sgr_gn_stage_fwd_bf16 / _bwd_bf16).  Loads convert to fp32 (gn_in), stores round once (gn_out); the arithmetic, the
+// mapping of logical elements to threads and the order of every sum are the same, so a bf16 result is the fp32 result on the upcast input,
+// rounded once.  A run of four bf16 values is one 64-bit access (Vec4h / aligned8).  The resize forms are fp32 only.
 #include "sgr_gn_stage.h"
 #include "sgr_launch.h"
 #include "sgr_reduce.h"       // wave_sum, Vec<4>, aligned16
@@ -30,6 +35,34 @@ constexpr int kGSliceMin = 32768;      // elements of a group per moments workgr
 constexpr int kGSliceMax = 64;         // moments workgroups per (b, g), at most: one wave folds them
 
 struct GnStrides { long long b, c, h, w; };
+
+// A run of four consecutive elements of the I/O type T as one access, to and from fp32: 128 bits of an fp32 tensor (Vec<4>), 64 bits of a
+// bf16 one (Vec4h).  The same four logical elements either way, so the sums below take them in the same order.
+__device__ __forceinline__ void ld4(const float* __restrict__ p, float (&v)[4]) {
+  const Vec<4> q = *reinterpret_cast<const Vec<4>*>(p);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = q.v[u];
+}
+__device__ __forceinline__ void ld4(const bf16* __restrict__ p, float (&v)[4]) {
+  const Vec4h q = *reinterpret_cast<const Vec4h*>(p);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = bf16_up(q.v[u]);
+}
+__device__ __forceinline__ void st4(float* __restrict__ p, const float (&v)[4]) {
+  Vec<4> q;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) q.v[u] = v[u];
+  *reinterpret_cast<Vec<4>*>(p) = q;
+}
+__device__ __forceinline__ void st4(bf16* __restrict__ p, const float (&v)[4]) {
+  Vec4h q;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) q.v[u] = bf16_round(v[u]);
+  *reinterpret_cast<Vec4h*>(p) = q;
+}
+// host side: every pointer on the boundary a run of four T needs
+template <typename T>
+static bool aligned_run(std::initializer_list<const void*> ptrs) { return sizeof(T) == 4 ? aligned16(ptrs) : aligned8(ptrs); }
 
 // the block's sums in thread 0: wave_sum per wave, then the waves added in order (their number comes from blockDim: 64 or 256 threads)
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* lds) {
@@ -56,29 +89,27 @@ static long long gn_slice_len(long long n) {
 
 // partials[(b G + g) S + s] = (sum, sum of squares) over the logical elements [s L, (s+1) L) of the group; thread t takes the runs of four
 // at s L + 4 (k T + t), k = 0, 1, ..
-template <bool VEC>
-__global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const float* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W,
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const T* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W,
                                                                int HW, long long L) {
   __shared__ double lds[2 * kGThreads / 64];
   const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z, G = gridDim.y, S = gridDim.x;
   const long long n = (long long)cpg * HW;
   const long long e0 = (long long)s * L, e1 = e0 + L < n ? e0 + L : n;
-  const float* xb = x + (long long)b * xs.b + (long long)g * cpg * xs.c;
+  const T* xb = x + (long long)b * xs.b + (long long)g * cpg * xs.c;
   double sum = 0.0, sq = 0.0;
   for (long long e = e0 + 4ll * threadIdx.x; e < e1; e += 4ll * blockDim.x) {
     int c = (int)(e / HW), p = (int)(e - (long long)c * HW);
     float v[4];
     if (VEC) {
-      const Vec<4> q = *reinterpret_cast<const Vec<4>*>(xb + (long long)c * xs.c + p);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = q.v[u];
+      ld4(xb + (long long)c * xs.c + p, v);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         v[u] = 0.0f;
         if (e + u < e1) {
           const int h = p / W, w = p - h * W;
-          v[u] = xb[(long long)c * xs.c + (long long)h * xs.h + (long long)w * xs.w];
+          v[u] = gn_in(xb[(long long)c * xs.c + (long long)h * xs.h + (long long)w * xs.w]);
         }
         if (++p == HW) { p = 0; ++c; }
       }
@@ -125,10 +156,10 @@ __global__ __launch_bounds__(64) void gn_stats_kernel(const double* __restrict__
 }
 
 // plain form: y = relu(gn(x)); a thread takes runs of four plane elements
-template <bool VEC>
-__global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const T* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
                                                                    const float* __restrict__ bias, const double* __restrict__ partials,
-                                                                   float* __restrict__ stats, float* __restrict__ y, int C, int cpg, int W, int HW,
+                                                                   float* __restrict__ stats, T* __restrict__ y, int C, int cpg, int W, int HW,
                                                                    int S, float eps) {
   __shared__ float sh[4];
   const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
@@ -139,46 +170,46 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const float* 
     st[0] = mh; st[1] = ml; st[2] = rstd; st[3] = sh[3];
   }
   const float wc = weight[c], bc = bias[c];
-  const float* xp = x + (long long)b * xs.b + (long long)c * xs.c;
-  float* yp = y + ((long long)b * C + c) * HW;
+  const T* xp = x + (long long)b * xs.b + (long long)c * xs.c;
+  T* yp = y + ((long long)b * C + c) * HW;
 #pragma unroll 1
   for (int r = 0; r < kGRounds; ++r) {
     const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
     if (p >= HW) break;
-    Vec<4> q;
+    float q[4];
     if (VEC) {
-      q = *reinterpret_cast<const Vec<4>*>(xp + p);
+      ld4(xp + p, q);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int pu = p + u < HW ? p + u : HW - 1, h = pu / W, w = pu - h * W;
-        q.v[u] = xp[(long long)h * xs.h + (long long)w * xs.w];
+        q[u] = gn_in(xp[(long long)h * xs.h + (long long)w * xs.w]);
       }
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) q.v[u] = fmaxf(gn_pre(gn_xhat(q.v[u], mh, ml, rstd), wc, bc), 0.0f);
+    for (int u = 0; u < 4; ++u) q[u] = fmaxf(gn_pre(gn_xhat(q[u], mh, ml, rstd), wc, bc), 0.0f);
     if (VEC) {
-      *reinterpret_cast<Vec<4>*>(yp + p) = q;
+      st4(yp + p, q);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (p + u < HW) yp[p + u] = q.v[u];
+        if (p + u < HW) yp[p + u] = gn_out<T>(q[u]);
     }
   }
 }
 
 // upcat form: channel ch < C is normalised x, ch >= C is skip as it is.  A thread at (i, jj) reads source rows i-1 .. i+1 x columns
-// 2jj-1 .. 2jj+2 (clamped) and writes output rows 2i, 2i+1 x columns 4jj .. 4jj+3.  VEC: 128-bit stores (W even, 16-byte aligned result).
-template <bool VEC>
-__global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
+// 2jj-1 .. 2jj+2 (clamped) and writes output rows 2i, 2i+1 x columns 4jj .. 4jj+3.  VEC: one store per run of four (W even, a result aligned for st4).
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const T* __restrict__ x, GnStrides xs, const T* __restrict__ skip, GnStrides ss,
                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
                                                                 const double* __restrict__ partials, float* __restrict__ stats,
-                                                                float* __restrict__ out, int C, int Cs, int cpg, int H, int W, int S, float eps) {
+                                                                T* __restrict__ out, int C, int Cs, int cpg, int H, int W, int S, float eps) {
   __shared__ float sh[4];
   const int ch = blockIdx.y, b = blockIdx.z;
   const bool norm = ch < C;      // uniform in the workgroup
   float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
-  const float* src;
+  const T* src;
   GnStrides st;
   if (norm) {
     const int G = C / cpg, g = ch / cpg;
@@ -196,7 +227,7 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __r
     st = ss;
   }
   const int W2 = (W + 1) >> 1, OW = 2 * W;
-  float* op = out + ((long long)b * (C + Cs) + ch) * 4ll * H * W;
+  T* op = out + ((long long)b * (C + Cs) + ch) * 4ll * H * W;
   const unsigned sth = (unsigned)st.h, stw = (unsigned)st.w;      // in-plane offsets fit 31 bits (checked on the host)
   const UpTaps taps = up_taps();
   // the position (i, jj) of round 0 by one division, of the later rounds by steps of 256
@@ -213,20 +244,20 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __r
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float t = src[ro[a] + co[k]];
+        const float t = gn_in(src[ro[a] + co[k]]);
         v[a][k] = norm ? fmaxf(gn_pre(gn_xhat(t, mh, ml, rstd), wc, bc), 0.0f) : t;
       }
     const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
-    Vec<4> top, bot;
-    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top.v, bot.v);
-    float* o0 = op + (long long)(2 * i) * OW + 4 * jj;
+    float top[4], bot[4];
+    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top, bot);
+    T* o0 = op + (long long)(2 * i) * OW + 4 * jj;
     if (VEC) {
-      *reinterpret_cast<Vec<4>*>(o0) = top;
-      *reinterpret_cast<Vec<4>*>(o0 + OW) = bot;
+      st4(o0, top);
+      st4(o0 + OW, bot);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (4 * jj + k < OW) { o0[k] = top.v[k]; o0[OW + k] = bot.v[k]; }
+        if (4 * jj + k < OW) { o0[k] = gn_out<T>(top[k]); o0[OW + k] = gn_out<T>(bot[k]); }
     }
     i += di;
     jj += dj;
@@ -235,9 +266,9 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const float* __r
 }
 
 // The upsample's adjoint at the source pixels (i, 2jj) and (i, 2jj+1) of an H x W plane: gp is the cotangent's plane [2H, 2W], the six weight
-// sets are up_adj_sets' of either axis.  VEC: the four inner columns of a row as one 128-bit load (W even, 16-byte aligned cotangent).
-template <bool VEC>
-__device__ __forceinline__ void up_gather(const float* __restrict__ gp, int i, int jj, int H, int W, const float (&rl)[4], const float (&rm)[4],
+// sets are up_adj_sets' of either axis.  VEC: the four inner columns of a row as one load (W even, a cotangent aligned for runs of four).
+template <bool VEC, typename T>
+__device__ __forceinline__ void up_gather(const T* __restrict__ gp, int i, int jj, int H, int W, const float (&rl)[4], const float (&rm)[4],
                                           const float (&rh)[4], const float (&cl)[4], const float (&cm)[4], const float (&chi)[4], float& a0,
                                           float& a1) {
   const int c0 = 2 * jj, OW = 2 * W, OH = 2 * H;
@@ -253,35 +284,36 @@ __device__ __forceinline__ void up_gather(const float* __restrict__ gp, int i, i
   for (int k = 0; k < 4; ++k) {
     const int orow = 2 * i - 1 + k;
     const bool in = orow >= 0 && orow < OH;
-    const float* row = gp + (long long)(in ? orow : 0) * OW;
+    const T* row = gp + (long long)(in ? orow : 0) * OW;
     const int o = 4 * jj;
-    gv[k][0] = in && o > 0 ? row[o - 1] : 0.0f;
+    gv[k][0] = in && o > 0 ? gn_in(row[o - 1]) : 0.0f;
     if (VEC) {
-      Vec<4> t{{0.0f, 0.0f, 0.0f, 0.0f}};
-      if (in) t = *reinterpret_cast<const Vec<4>*>(row + o);
+      float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (in) ld4(row + o, t);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) gv[k][1 + u] = t.v[u];
+      for (int u = 0; u < 4; ++u) gv[k][1 + u] = t[u];
     } else {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) gv[k][1 + u] = in && o + u < OW ? row[o + u] : 0.0f;
+      for (int u = 0; u < 4; ++u) gv[k][1 + u] = in && o + u < OW ? gn_in(row[o + u]) : 0.0f;
     }
-    gv[k][5] = in && o + 4 < OW ? row[o + 4] : 0.0f;
+    gv[k][5] = in && o + 4 < OW ? gn_in(row[o + 4]) : 0.0f;
   }
   up_adjoint(gv, wr, wa, wb, a0, a1);
 }
 
 // Backward pass 1 over the channels [c_begin, c_begin + gridDim.y) of cat([y, skip]).  UP: g is [B,C+Cs,2H,2W] and the adjoint is gathered;
 // otherwise g is [B,C,H,W] and taken as it is.  ch < C: dy = (y > 0) adjoint, stored to `dy` (if given) and summed; ch >= C: dskip = adjoint.
-template <bool VEC, bool UP>
-__global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __restrict__ g, const float* __restrict__ x, GnStrides xs,
+// The cotangent, x and dskip have the I/O type T; `dy` is workspace and stays fp32 (the unrounded masked adjoint, as in the fp32 operator).
+template <bool VEC, bool UP, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __restrict__ g, const T* __restrict__ x, GnStrides xs,
                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                 const float* __restrict__ stats, float* __restrict__ dy, float* __restrict__ dskip,
+                                                                 const float* __restrict__ stats, float* __restrict__ dy, T* __restrict__ dskip,
                                                                  double* __restrict__ partials, int C, int Cs, int cpg, int H, int W, int c_begin) {
   __shared__ double lds[2 * kGThreads / 64];
   const int ch = c_begin + blockIdx.y, b = blockIdx.z, P = gridDim.x;
   const bool norm = ch < C;
   float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
-  const float* xp = nullptr;
+  const T* xp = nullptr;
   if (norm) {
     const float* st = stats + 4 * ((long long)b * (C / cpg) + ch / cpg);
     mh = st[0]; ml = st[1]; rstd = st[2];
@@ -289,8 +321,9 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __
     xp = x + (long long)b * xs.b + (long long)ch * xs.c;
   }
   const int W2 = (W + 1) >> 1, OW = UP ? 2 * W : W, OH = UP ? 2 * H : H;
-  const float* gp = g + ((long long)b * (C + Cs) + ch) * (long long)OH * OW;
-  float* dst = norm ? (dy ? dy + ((long long)b * C + ch) * H * W : nullptr) : dskip + ((long long)b * Cs + (ch - C)) * H * W;
+  const T* gp = g + ((long long)b * (C + Cs) + ch) * (long long)OH * OW;
+  float* dyp = norm && dy ? dy + ((long long)b * C + ch) * H * W : nullptr;
+  T* dsp = norm ? nullptr : dskip + ((long long)b * Cs + (ch - C)) * H * W;
   double s1 = 0.0, s2 = 0.0;
   const unsigned sh = (unsigned)xs.h, sw = (unsigned)xs.w;      // in-plane offsets fit 31 bits (checked on the host)
   float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];      // the adjoint weights at the low edge, inside and at the high edge of either axis
@@ -305,12 +338,12 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __
     if (UP) {
       up_gather<VEC>(gp, i, jj, H, W, rl, rm, rh, cl, cm, chi, a0, a1);
     } else {
-      a0 = gp[(long long)i * W + c0];
-      a1 = two ? gp[(long long)i * W + c0 + 1] : 0.0f;
+      a0 = gn_in(gp[(long long)i * W + c0]);
+      a1 = two ? gn_in(gp[(long long)i * W + c0 + 1]) : 0.0f;
     }
     if (norm) {
-      const float x0 = xp[(unsigned)i * sh + (unsigned)c0 * sw];
-      const float x1 = two ? xp[(unsigned)i * sh + (unsigned)(c0 + 1) * sw] : 0.0f;
+      const float x0 = gn_in(xp[(unsigned)i * sh + (unsigned)c0 * sw]);
+      const float x1 = two ? gn_in(xp[(unsigned)i * sh + (unsigned)(c0 + 1) * sw]) : 0.0f;
       const float h0 = gn_xhat(x0, mh, ml, rstd), h1 = gn_xhat(x1, mh, ml, rstd);
       a0 = gn_pre(h0, wc, bc) > 0.0f ? a0 : 0.0f;
       a1 = two && gn_pre(h1, wc, bc) > 0.0f ? a1 : 0.0f;
@@ -319,9 +352,12 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const float* __
       s2 = fma((double)a0, (double)h0, s2);
       s2 = fma((double)a1, (double)h1, s2);
     }
-    if (dst) {
-      dst[(long long)i * W + c0] = a0;
-      if (two) dst[(long long)i * W + c0 + 1] = a1;
+    if (dyp) {
+      dyp[(long long)i * W + c0] = a0;
+      if (two) dyp[(long long)i * W + c0 + 1] = a1;
+    } else if (dsp) {
+      dsp[(long long)i * W + c0] = gn_out<T>(a0);
+      if (two) dsp[(long long)i * W + c0 + 1] = gn_out<T>(a1);
     }
     i += di;
     jj += dj;
@@ -376,46 +412,47 @@ __global__ __launch_bounds__(64) void gn_bwd_fold_kernel(const double* __restric
 }
 
 // dx from dy (MASK = false: pass 1's masked adjoint) or from the cotangent itself (MASK = true: the plain form, masked here)
-template <bool VEC, bool MASK>
-__global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const float* __restrict__ dy, const float* __restrict__ x, GnStrides xs,
+// x and dx have the I/O type T; dy has TD: float for pass 1's workspace, T for the cotangent
+template <bool VEC, bool MASK, typename T, typename TD>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const TD* __restrict__ dy, const T* __restrict__ x, GnStrides xs,
                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
                                                                  const float* __restrict__ stats, const float* __restrict__ coef,
-                                                                 float* __restrict__ dx, int C, int cpg, int W, int HW) {
+                                                                 T* __restrict__ dx, int C, int cpg, int W, int HW) {
   const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
   const float* st = stats + 4 * ((long long)b * G + g);
   const float mh = st[0], ml = st[1], rstd = st[2], wc = weight[c], bc = bias[c];
   const float c1 = coef[2 * (b * G + g)], c2 = coef[2 * (b * G + g) + 1];
-  const float* xp = x + (long long)b * xs.b + (long long)c * xs.c;
-  const float* dp = dy + ((long long)b * C + c) * HW;
-  float* op = dx + ((long long)b * C + c) * HW;
+  const T* xp = x + (long long)b * xs.b + (long long)c * xs.c;
+  const TD* dp = dy + ((long long)b * C + c) * HW;
+  T* op = dx + ((long long)b * C + c) * HW;
 #pragma unroll 1
   for (int r = 0; r < kGRounds; ++r) {
     const int p = 4 * ((blockIdx.x * kGRounds + r) * kGThreads + threadIdx.x);
     if (p >= HW) break;
-    Vec<4> xv, dv;
+    float xv[4], dv[4];
     if (VEC) {
-      xv = *reinterpret_cast<const Vec<4>*>(xp + p);
-      dv = *reinterpret_cast<const Vec<4>*>(dp + p);
+      ld4(xp + p, xv);
+      ld4(dp + p, dv);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int pu = p + u < HW ? p + u : HW - 1, h = pu / W, w = pu - h * W;
-        xv.v[u] = xp[(long long)h * xs.h + (long long)w * xs.w];
-        dv.v[u] = dp[pu];
+        xv[u] = gn_in(xp[(long long)h * xs.h + (long long)w * xs.w]);
+        dv[u] = gn_in(dp[pu]);
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float xh = gn_xhat(xv.v[u], mh, ml, rstd);
-      const float d = !MASK || gn_pre(xh, wc, bc) > 0.0f ? dv.v[u] : 0.0f;
-      dv.v[u] = gn_dx(d, xh, wc, rstd, c1, c2);
+      const float xh = gn_xhat(xv[u], mh, ml, rstd);
+      const float d = !MASK || gn_pre(xh, wc, bc) > 0.0f ? dv[u] : 0.0f;
+      dv[u] = gn_dx(d, xh, wc, rstd, c1, c2);
     }
     if (VEC) {
-      *reinterpret_cast<Vec<4>*>(op + p) = dv;
+      st4(op + p, dv);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (p + u < HW) op[p + u] = dv.v[u];
+        if (p + u < HW) op[p + u] = gn_out<T>(dv[u]);
     }
   }
 }
@@ -642,9 +679,11 @@ __global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float*
   }
 }
 
-// the planes of t are rows of W consecutive floats, H W % 4 == 0, and every plane starts on a 16-byte boundary
-static bool g_plane_vec(const float* t, const GnStrides& s, int H, int W) {
-  return s.w == 1 && s.h == W && (long long)H * W % 4 == 0 && s.c % 4 == 0 && s.b % 4 == 0 && aligned16({t});
+// the planes of t are rows of W consecutive elements, H W % 4 == 0, and every plane starts on the boundary of a run of four (16 bytes of
+// fp32, 8 of bf16)
+template <typename T>
+static bool g_plane_vec(const T* t, const GnStrides& s, int H, int W) {
+  return s.w == 1 && s.h == W && (long long)H * W % 4 == 0 && s.c % 4 == 0 && s.b % 4 == 0 && aligned_run<T>({t});
 }
 // non-negative strides whose largest in-plane offset fits 31 bits: the kernels index a plane with 32-bit offsets
 static bool g_plane_fits(const long long* s, int H, int W) {
@@ -675,9 +714,11 @@ extern "C" long long sgr_gn_stage_workspace_floats(int B, int C, int G, int H, i
   return 4ll * B * C * g_bwd_slices(H, W) + g_coef_floats(B, G) + (upcat ? (long long)B * C * HW : 0);
 }
 
-extern "C" int sgr_gn_stage_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
-                                int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps,
-                                void* stream) {
+// sgr_gn_stage_fwd / _bwd and their bf16 forms: one body, instantiated on the type T of x, skip, the result, the cotangent, dx and dskip.
+// The refusals and their messages are the fp32 entry points' for both.
+template <typename T>
+static int gn_stage_fwd_t(const T* x, const float* weight, const float* bias, const T* skip, T* out, float* stats, float* workspace, int B, int C, int G, int Cs,
+                          int H, int W, const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
   SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, "sgr_gn_stage_fwd: NULL tensor");
   SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), "sgr_gn_stage_fwd: skip and its channel count do not agree");
   GN_CHECK_SIZES("sgr_gn_stage_fwd");
@@ -694,28 +735,28 @@ extern "C" int sgr_gn_stage_fwd(const float* x, const float* weight, const float
   const bool xvec = g_plane_vec(x, xs, H, W);
   const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
   if (xvec)
-    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<true, T>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   else
-    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<false, T>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   if (!skip) {
     const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-    if (xvec && aligned16({out}))
-      hipLaunchKernelGGL(gn_apply_plain_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+    if (xvec && aligned_run<T>({out}))
+      hipLaunchKernelGGL((gn_apply_plain_kernel<true, T>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
     else
-      hipLaunchKernelGGL(gn_apply_plain_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+      hipLaunchKernelGGL((gn_apply_plain_kernel<false, T>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
   } else {
     const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C + Cs, B);
-    if (W % 2 == 0 && aligned16({out}))
-      hipLaunchKernelGGL(gn_apply_up_kernel<true>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+    if (W % 2 == 0 && aligned_run<T>({out}))
+      hipLaunchKernelGGL((gn_apply_up_kernel<true, T>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
     else
-      hipLaunchKernelGGL(gn_apply_up_kernel<false>, grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+      hipLaunchKernelGGL((gn_apply_up_kernel<false, T>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_fwd");
 }
 
-extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
-                                float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
-                                void* stream) {
+template <typename T>
+static int gn_stage_bwd_t(const T* g, const T* x, const float* weight, const float* bias, const float* stats, T* dx, float* dweight, float* dbias, T* dskip,
+                          float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, void* stream) {
   SGR_REQUIRE(g, "sgr_gn_stage_bwd: NULL cotangent");
   SGR_REQUIRE(dx || dweight || dbias || dskip, "sgr_gn_stage_bwd: no gradient requested");
   const bool side = dx || dweight || dbias;      // anything behind the normalisation
@@ -735,12 +776,12 @@ extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* wei
   const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
   const dim3 grid1(P, c_end - c_begin, B);
   if (up) {
-    if (W % 2 == 0 && aligned16({g}))
-      hipLaunchKernelGGL((gn_bwd_pass1_kernel<true, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+    if (W % 2 == 0 && aligned_run<T>({g}))
+      hipLaunchKernelGGL((gn_bwd_pass1_kernel<true, true, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
     else
-      hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, true>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+      hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, true, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
   } else {
-    hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, false>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
+    hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, false, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
   }
   if (side) {
     const int jobs = B * G + ((dweight || dbias) ? C : 0);
@@ -748,17 +789,41 @@ extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* wei
   }
   if (dx) {
     const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-    const float* d = up ? dy : g;
-    const bool vec = g_plane_vec(x, xs, H, W) && aligned16({d, dx});
-    if (up) {
-      if (vec) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-    } else {
-      if (vec) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, true>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, true>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+    const bool xvec = g_plane_vec(x, xs, H, W) && aligned_run<T>({dx});
+    if (up) {      // from pass 1's fp32 `dy`
+      const float* d = dy;
+      if (xvec && aligned16({d})) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false, T, float>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false, T, float>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+    } else {       // from the cotangent itself
+      if (xvec && aligned_run<T>({g})) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, true, T, T>), grid2, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, true, T, T>), grid2, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
     }
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_bwd");
+}
+
+extern "C" int sgr_gn_stage_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
+                                int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps,
+                                void* stream) {
+  return gn_stage_fwd_t<float>(x, weight, bias, skip, out, stats, workspace, B, C, G, Cs, H, W, x_strides, skip_strides, eps, stream);
+}
+extern "C" int sgr_gn_stage_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
+                                float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
+                                void* stream) {
+  return gn_stage_bwd_t<float>(g, x, weight, bias, stats, dx, dweight, dbias, dskip, workspace, B, C, G, Cs, H, W, x_strides, stream);
+}
+// bf16 bit patterns travel as unsigned short through the C ABI
+extern "C" int sgr_gn_stage_fwd_bf16(const unsigned short* x, const float* weight, const float* bias, const unsigned short* skip, unsigned short* out,
+                                     float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides,
+                                     const long long* skip_strides, float eps, void* stream) {
+  return gn_stage_fwd_t<bf16>(reinterpret_cast<const bf16*>(x), weight, bias, reinterpret_cast<const bf16*>(skip), reinterpret_cast<bf16*>(out), stats, workspace, B,
+                              C, G, Cs, H, W, x_strides, skip_strides, eps, stream);
+}
+extern "C" int sgr_gn_stage_bwd_bf16(const unsigned short* g, const unsigned short* x, const float* weight, const float* bias, const float* stats,
+                                     unsigned short* dx, float* dweight, float* dbias, unsigned short* dskip, float* workspace, int B, int C, int G, int Cs,
+                                     int H, int W, const long long* x_strides, void* stream) {
+  return gn_stage_bwd_t<bf16>(reinterpret_cast<const bf16*>(g), reinterpret_cast<const bf16*>(x), weight, bias, stats, reinterpret_cast<bf16*>(dx), dweight, dbias,
+                              reinterpret_cast<bf16*>(dskip), workspace, B, C, G, Cs, H, W, x_strides, stream);
 }
 
 // ---- resize-to-skip entry points ------------------------------------------------------------------------------------------------------------
@@ -802,9 +867,9 @@ extern "C" int sgr_gn_resize_fwd(const float* x, const float* weight, const floa
   hipStream_t st = (hipStream_t)stream;
   const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
   if (g_plane_vec(x, xs, H, W))
-    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<true, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   else
-    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<false, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   const bool samew = W == Ws;
 #define RS_LAUNCH(kernel, vec, grid, ...)                                                                                   \
   do {                                                                                                                      \
@@ -869,9 +934,9 @@ extern "C" int sgr_gn_resize_bwd(const float* g, const float* x, const float* we
     if (dx) {
       const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
       if (g_plane_vec(x, xs, H, W) && aligned16({dy, dx}))
-        hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+        hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false, float, float>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
       else
-        hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+        hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false, float, float>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
     }
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_bwd");
@@ -896,9 +961,9 @@ extern "C" int sgr_gn_moments(const float* x, float* stats, float* workspace, in
   // the launch of sgr_gn_stage_fwd: the same partials, and gn_group_stat folds them to the same bits
   const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
   if (g_plane_vec(x, xs, H, W))
-    hipLaunchKernelGGL(gn_moments_kernel<true>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<true, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   else
-    hipLaunchKernelGGL(gn_moments_kernel<false>, mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+    hipLaunchKernelGGL((gn_moments_kernel<false, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, st, partials, stats, S, (double)n, eps);
   return sgr_check((int)hipGetLastError(), "sgr_gn_moments");
 }

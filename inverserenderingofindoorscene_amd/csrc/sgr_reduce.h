@@ -1,4 +1,4 @@
-// The reduction scheme and the 1-or-4 float vector access of the streaming operators (sgr_loss.hip, sgr_brdf_loss.hip, sgr_brdf_input.hip,
+// The reduction scheme and the 1-or-4 float (or 4 bf16) vector access of the streaming operators (sgr_loss.hip, sgr_brdf_loss.hip, sgr_brdf_input.hip,
 // sgr_glue.hip, sgr_brdf_heads.hip, sgr_gn_stage.hip, sgr_final_conv.hip, sgr_recon.hip / sgr_recon_fold.h), one definition each:
 //   fp32 per-thread partials -> wave ladder -> the four wave sums through LDS -> ONE partial per workgroup in a workspace -> folded in
 //   double, in a fixed order, by the consumer's prologue.  No float atomics, no host synchronisation.
@@ -118,6 +118,16 @@ __device__ __forceinline__ void stv(float* __restrict__ p, size_t i, const Vec<V
 static inline bool aligned16(std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs)
     if ((uintptr_t)p & 15) return false;
+  return true;
+}
+
+// ---- four consecutive 16-bit elements (bf16 bit patterns) as one access -----------------------------------------------------------------
+// Vec4h is a 64-bit load / store: the address must be 8-byte aligned (aligned8 below, and an element offset that is a multiple of four).
+// It covers the four elements Vec<4> covers of an fp32 tensor, so a kernel instantiated on either type gives a thread the same run.
+struct alignas(8) Vec4h { unsigned short v[4]; };
+static inline bool aligned8(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 7) return false;
   return true;
 }
 

@@ -1,0 +1,85 @@
+// torch.autocast rules for torch.ops.sgrender.* (DESIGN.md section 8j): what an operator does with its floating tensors when it is called
+// inside `with torch.autocast('cuda', dtype=...)`.  With autocast off the Autocast key is not in the dispatch set and nothing here runs.
+//
+//   fp32 policy   every functional operator but gn_stage / gn_stage_bwd: floating tensors (optional ones and lists included) are cast to
+//                 fp32 and the result is fp32 -- what PyTorch does for its own group_norm, losses and interpolate.  The render layer, the
+//                 objectives, the solver, the heads and the exact-fp32 MFMA convolutions have fp32 kernels only.
+//   gn_stage      a bf16 x stays bf16 and skip is cast to it (native bf16 kernels, sgr_gn_stage.hip); anything else -- an fp16 x under an
+//                 fp16 autocast too -- is cast to fp32 with its skip.  weight and bias are cast to fp32 either way.
+//   gn_stage_bwd  the same rule on (cotangent, x): bf16 stays when x (or, without x, the cotangent) is bf16.
+//   fall through  operators that write into an argument (rescale_grads_, rescale_grads6_, allreduce_sum_, light_objective_stage2(_brdf):
+//                 a cast copy would take the write) and those without a tensor argument: no kernel here, PyTorch's fall-through applies.
+//
+// Written with at::autocast::cached_cast under an ExcludeDispatchKeyGuard, as PyTorch's own rules are: the casts are ordinary differentiable
+// `to` calls, so the gradients come back in the callers' dtypes.
+#include <ATen/autocast_mode.h>
+
+#include "sgr_torch_common.hpp"
+
+namespace {
+
+using namespace sgr_host;
+using OT = OptTensor;
+using at::autocast::cached_cast;
+
+constexpr auto kDev = c10::DeviceType::CUDA;
+c10::DispatchKeySet autocast_keys() { return c10::DispatchKeySet(c10::DispatchKey::AutocastCUDA); }
+
+// fp32 policy for any schema: the arguments are cast on the stack, then the operator is called again below the Autocast key
+void autocast_fp32(const c10::OperatorHandle& op, torch::jit::Stack* stack) {
+  c10::impl::ExcludeDispatchKeyGuard no_autocast(autocast_keys());
+  const size_t n = op.schema().arguments().size(), base = stack->size() - n;
+  for (size_t i = 0; i < n; ++i) {
+    c10::IValue& v = (*stack)[base + i];
+    if (v.isTensor()) {      // Tensor and a Tensor? that is given
+      v = cached_cast(at::kFloat, v.toTensor(), kDev);
+    } else if (v.isTensorList()) {
+      v = cached_cast(at::kFloat, v.toTensorVector(), kDev);
+    }
+  }
+  op.callBoxed(stack);
+}
+
+using FwdSig = T2(const Tensor&, const Tensor&, const Tensor&, const OT&, int64_t, double);
+using BwdSig = T4(const Tensor&, const OT&, const OT&, const OT&, const OT&, int64_t, int64_t, int64_t, bool, bool, bool, bool);
+
+at::ScalarType io_type_of(const Tensor& t) { return t.scalar_type() == at::kBFloat16 ? at::kBFloat16 : at::kFloat; }
+
+T2 gn_stage_autocast(const Tensor& x, const Tensor& weight, const Tensor& bias, const OT& skip, int64_t G, double eps) {
+  c10::impl::ExcludeDispatchKeyGuard no_autocast(autocast_keys());
+  const at::ScalarType io = io_type_of(x);
+  static auto op = find_op<FwdSig>("sgrender::gn_stage");
+  return op.call(cached_cast(io, x, kDev), cached_cast(at::kFloat, weight, kDev), cached_cast(at::kFloat, bias, kDev), cached_cast(io, skip, kDev), G, eps);
+}
+
+T4 gn_stage_bwd_autocast(const Tensor& g, const OT& x, const OT& weight, const OT& bias, const OT& stats, int64_t C, int64_t Cs, int64_t G, bool nX, bool nW, bool nB,
+                         bool nS) {
+  c10::impl::ExcludeDispatchKeyGuard no_autocast(autocast_keys());
+  const at::ScalarType io = io_type_of(x.has_value() && x->defined() ? *x : g);
+  static auto op = find_op<BwdSig>("sgrender::gn_stage_bwd");
+  return op.call(cached_cast(io, g, kDev), cached_cast(io, x, kDev), cached_cast(at::kFloat, weight, kDev), cached_cast(at::kFloat, bias, kDev),
+                 cached_cast(at::kFloat, stats, kDev), C, Cs, G, nX, nW, nB, nS);
+}
+
+// every functional operator with a tensor argument, file by file as they are defined
+constexpr const char* kFp32Ops[] = {
+    // sgr_torch.cpp
+    "sg_to_env", "sg_to_env_bwd", "render_env", "render_env_bwd_env", "render_bwd_brdf", "fused_render", "fused_render_bwd_sg", "lsregress_coef",
+    "lsregress_diffspec_coef", "render_loss", "render_loss_finalize", "render_loss_bwd", "recon_loss_parts", "recon_loss_bwd", "light_heads", "light_heads_bwd",
+    "sg_shading", "light_albedo_scale", "light_encoder_input", "attach_grads", "light_objective_fwdbwd", "light_objective", "light_objective_stage1",
+    "light_objective_stage3", "attach_grads6", "light_objective_brdf_fwdbwd", "light_objective_brdf", "comm_init",
+    // sgr_torch_brdf.cpp
+    "brdf_objective_fwd", "brdf_objective_finalize", "brdf_objective_bwd", "brdf_objective", "batch_ranking_loss_fwd", "batch_ranking_loss_bwd", "batch_ranking_loss",
+    // sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_bilateral.cpp
+    "brdf_encoder_input", "brdf_heads", "brdf_heads_bwd", "bilateral_grid", "bilateral_solve_fwd", "bilateral_solve_bwd", "bilateral_solve",
+    // sgr_torch_gn_resize.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp
+    "gn_resize", "gn_resize_bwd", "final_conv", "final_conv_bwd", "light_final_conv", "light_final_conv_bwd", "encoder_conv", "encoder_conv_bwd",
+};
+
+}  // namespace
+
+TORCH_LIBRARY_IMPL(sgrender, Autocast, m) {
+  for (const char* name : kFp32Ops) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&autocast_fp32>());
+  m.impl("gn_stage", &gn_stage_autocast);
+  m.impl("gn_stage_bwd", &gn_stage_bwd_autocast);
+}

@@ -14,6 +14,12 @@ using OT = OptTensor;
 
 bool has(const OT& t) { return t.has_value() && t->defined(); }
 
+// the element types of x, skip, the result, the cotangent, dx and dskip; everything else is fp32
+bool io_type(at::ScalarType t) { return t == at::kFloat || t == at::kBFloat16; }
+// a bf16 tensor's elements as the C ABI takes them; absent and empty tensors are NULL
+const unsigned short* hrp(const Tensor& t) { return t.defined() && t.numel() ? static_cast<const unsigned short*>(t.const_data_ptr()) : nullptr; }
+unsigned short* hwp(const Tensor& t) { return t.defined() && t.numel() ? static_cast<unsigned short*>(t.mutable_data_ptr()) : nullptr; }
+
 struct Stage {
   int64_t B = 0, C = 0, Cs = 0, H = 0, W = 0, G = 0;
   bool up() const { return Cs > 0; }
@@ -34,8 +40,15 @@ void check_sizes(const Stage& s) {
 // shared by the device and the Meta kernels: a traced graph cannot pass tracing and then fail on the device
 Stage check_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias, const OT& skip, int64_t G, double eps, bool device) {
   if (device) TORCH_CHECK(x.is_cuda() && weight.is_cuda() && bias.is_cuda() && (!has(skip) || skip->is_cuda()), kNoCpu);
-  TORCH_CHECK(x.scalar_type() == at::kFloat && weight.scalar_type() == at::kFloat && bias.scalar_type() == at::kFloat &&
-                  (!has(skip) || skip->scalar_type() == at::kFloat),
+  // x and skip: fp32, or bf16 together; weight and bias: fp32 either way, as autocast leaves parameters
+  const auto xt = x.scalar_type();
+  if (has(skip) && io_type(xt) && io_type(skip->scalar_type()))
+    TORCH_CHECK(skip->scalar_type() == xt, "sgrender: gn_stage: x and skip must have one dtype, got x ", xt, " and skip ", skip->scalar_type(),
+                "; cast one of them (under torch.autocast the operator casts skip to x's dtype itself)");
+  if (xt == at::kBFloat16)
+    TORCH_CHECK(weight.scalar_type() == at::kFloat && bias.scalar_type() == at::kFloat, "sgrender: gn_stage: a bf16 x takes fp32 weight and bias (the parameters stay fp32, as "
+                "under torch.autocast), got weight ", weight.scalar_type(), " and bias ", bias.scalar_type());
+  TORCH_CHECK(io_type(xt) && weight.scalar_type() == at::kFloat && bias.scalar_type() == at::kFloat && (!has(skip) || skip->scalar_type() == xt),
               "sgrender: gn_stage: fp32 tensors required (x ", x.scalar_type(), ", weight ", weight.scalar_type(), ", bias ", bias.scalar_type(),
               has(skip) ? ", skip " : "", has(skip) ? c10::toString(skip->scalar_type()) : "", ")");
   TORCH_CHECK(x.dim() == 4, "sgrender: gn_stage: x must be [B,C,H,W], got ", x.sizes());
@@ -70,10 +83,16 @@ Tensor workspace(const Stage& s, bool backward, const at::TensorOptions& o) {
 T2 gn_stage_cuda(const Tensor& x, const Tensor& weight, const Tensor& bias, const OT& skip, int64_t G, double eps) {
   const Stage s = check_fwd(x, weight, bias, skip, G, eps, true);
   const c10::DeviceGuard guard(x.device());
-  const auto o = x.options().memory_format(at::MemoryFormat::Contiguous);
-  Tensor out = at::empty(s.out_sizes(), o), stats = at::empty({s.B, s.G, 4}, o);
-  const Tensor w = weight.contiguous(), b = bias.contiguous(), ws = workspace(s, false, o);
+  const auto o = x.options().memory_format(at::MemoryFormat::Contiguous), of = o.dtype(at::kFloat);
+  Tensor out = at::empty(s.out_sizes(), o), stats = at::empty({s.B, s.G, 4}, of);
+  const Tensor w = weight.contiguous(), b = bias.contiguous(), ws = workspace(s, false, of);
   const Strides4 xs = strides_of(x), ss = has(skip) ? strides_of(*skip) : Strides4{};
+  if (x.scalar_type() == at::kBFloat16) {
+    ok(api().sgr_gn_stage_fwd_bf16(hrp(x), rp(w), rp(b), has(skip) ? hrp(*skip) : nullptr, hwp(out), wp(stats), wp(ws), (int)s.B, (int)s.C, (int)s.G, (int)s.Cs,
+                                   (int)s.H, (int)s.W, xs.v, has(skip) ? ss.v : nullptr, (float)eps, stream_of(x.device())),
+       "sgr_gn_stage_fwd_bf16");
+    return {out, stats};
+  }
   ok(api().sgr_gn_stage_fwd(rp(x), rp(w), rp(b), has(skip) ? rp(*skip) : nullptr, wp(out), wp(stats), wp(ws), (int)s.B, (int)s.C, (int)s.G, (int)s.Cs, (int)s.H,
                             (int)s.W, xs.v, has(skip) ? ss.v : nullptr, (float)eps, stream_of(x.device())),
      "sgr_gn_stage_fwd");
@@ -82,7 +101,7 @@ T2 gn_stage_cuda(const Tensor& x, const Tensor& weight, const Tensor& bias, cons
 T2 gn_stage_meta(const Tensor& x, const Tensor& weight, const Tensor& bias, const OT& skip, int64_t G, double eps) {
   const Stage s = check_fwd(x, weight, bias, skip, G, eps, false);
   const auto o = x.options().memory_format(at::MemoryFormat::Contiguous);
-  return {at::empty(s.out_sizes(), o), at::empty({s.B, s.G, 4}, o)};
+  return {at::empty(s.out_sizes(), o), at::empty({s.B, s.G, 4}, o.dtype(at::kFloat))};
 }
 
 // the backward's own checks; x / weight / bias / stats may be None when only dskip is wanted
@@ -91,8 +110,8 @@ Stage check_bwd(const Tensor& g, const OT& x, const OT& weight, const OT& bias, 
   TORCH_CHECK(nX || nW || nB || nS, "sgrender: gn_stage_bwd: no gradient requested");
   TORCH_CHECK(!nS || Cs > 0, "sgrender: gn_stage_bwd: a skip gradient requested without skip channels");
   if (device) TORCH_CHECK(g.is_cuda(), kNoCpu);
-  TORCH_CHECK(g.dim() == 4 && g.scalar_type() == at::kFloat && C > 0 && Cs >= 0 && g.size(1) == C + Cs, "sgrender: gn_stage_bwd: the cotangent must be fp32 [B,", C + Cs,
-              ",.,.], got ", g.scalar_type(), " ", g.sizes());
+  TORCH_CHECK(g.dim() == 4 && io_type(g.scalar_type()) && C > 0 && Cs >= 0 && g.size(1) == C + Cs, "sgrender: gn_stage_bwd: the cotangent must be fp32 or bf16 [B,",
+              C + Cs, ",.,.], got ", g.scalar_type(), " ", g.sizes());
   Stage s;
   s.B = g.size(0); s.C = C; s.Cs = Cs; s.G = G;
   s.H = Cs > 0 ? g.size(2) / 2 : g.size(2);
@@ -102,8 +121,10 @@ Stage check_bwd(const Tensor& g, const OT& x, const OT& weight, const OT& bias, 
   if (nX || nW || nB) {
     TORCH_CHECK(has(x) && has(weight) && has(bias) && has(stats), "sgrender: gn_stage_bwd: x, weight, bias and stats are needed for dx, dweight and dbias");
     if (device) TORCH_CHECK(x->is_cuda() && weight->is_cuda() && bias->is_cuda() && stats->is_cuda(), kNoCpu);
-    TORCH_CHECK(x->scalar_type() == at::kFloat && x->sizes() == at::IntArrayRef({s.B, s.C, s.H, s.W}), "sgrender: gn_stage_bwd: x must be fp32 [", s.B, ",", s.C, ",", s.H, ",",
-                s.W, "], got ", x->scalar_type(), " ", x->sizes());
+    TORCH_CHECK(!io_type(x->scalar_type()) || x->scalar_type() == g.scalar_type(), "sgrender: gn_stage_bwd: x and the cotangent must have one dtype, got x ",
+                x->scalar_type(), " and the cotangent ", g.scalar_type());
+    TORCH_CHECK(io_type(x->scalar_type()) && x->sizes() == at::IntArrayRef({s.B, s.C, s.H, s.W}), "sgrender: gn_stage_bwd: x must be fp32 or bf16 [", s.B, ",", s.C, ",", s.H,
+                ",", s.W, "], got ", x->scalar_type(), " ", x->sizes());
     TORCH_CHECK(weight->scalar_type() == at::kFloat && bias->scalar_type() == at::kFloat && weight->dim() == 1 && bias->dim() == 1 && weight->size(0) == s.C &&
                     bias->size(0) == s.C,
                 "sgrender: gn_stage_bwd: weight and bias must be fp32 [", s.C, "]");
@@ -112,11 +133,11 @@ Stage check_bwd(const Tensor& g, const OT& x, const OT& weight, const OT& bias, 
   }
   return s;
 }
-// a [0] tensor where a gradient is not wanted
+// a [0] tensor where a gradient is not wanted; dx and dskip in the cotangent's dtype (o), dweight and dbias in fp32
 T4 bwd_outputs(const Stage& s, const at::TensorOptions& o, bool nX, bool nW, bool nB, bool nS) {
-  auto none = [&] { return at::empty({0}, o); };
-  return {nX ? at::empty({s.B, s.C, s.H, s.W}, o) : none(), nW ? at::empty({s.C}, o) : none(), nB ? at::empty({s.C}, o) : none(),
-          nS ? at::empty({s.B, s.Cs, s.H, s.W}, o) : none()};
+  const auto of = o.dtype(at::kFloat);
+  return {at::empty(nX ? std::vector<int64_t>{s.B, s.C, s.H, s.W} : std::vector<int64_t>{0}, o), at::empty({nW ? s.C : 0}, of), at::empty({nB ? s.C : 0}, of),
+          at::empty(nS ? std::vector<int64_t>{s.B, s.Cs, s.H, s.W} : std::vector<int64_t>{0}, o)};
 }
 T4 gn_stage_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, const OT& bias, const OT& stats, int64_t C, int64_t Cs, int64_t G, bool nX, bool nW, bool nB,
                      bool nS) {
@@ -130,8 +151,15 @@ T4 gn_stage_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, const OT& b
   Strides4 xs{};
   if (side) {
     w = weight->contiguous(); b = bias->contiguous(); st = stats->contiguous();
-    ws = workspace(s, true, o);
+    ws = workspace(s, true, o.dtype(at::kFloat));
     xs = strides_of(*x);
+  }
+  if (g.scalar_type() == at::kBFloat16) {
+    ok(api().sgr_gn_stage_bwd_bf16(hrp(gc), side ? hrp(*x) : nullptr, rp(w), rp(b), rp(st), hwp(std::get<0>(out)), wp(std::get<1>(out)), wp(std::get<2>(out)),
+                                   hwp(std::get<3>(out)), wp(ws), (int)s.B, (int)s.C, (int)s.G, (int)s.Cs, (int)s.H, (int)s.W, side ? xs.v : nullptr,
+                                   stream_of(g.device())),
+       "sgr_gn_stage_bwd_bf16");
+    return out;
   }
   ok(api().sgr_gn_stage_bwd(rp(gc), side ? rp(*x) : nullptr, rp(w), rp(b), rp(st), wp(std::get<0>(out)), wp(std::get<1>(out)), wp(std::get<2>(out)),
                             wp(std::get<3>(out)), wp(ws), (int)s.B, (int)s.C, (int)s.G, (int)s.Cs, (int)s.H, (int)s.W, side ? xs.v : nullptr, stream_of(g.device())),

@@ -13,7 +13,12 @@
 
 Eager PyTorch spends four launches forward on a decoder stage (GroupNorm, ReLU, ``cat``, ``upsample_bilinear2d``) and keeps three maps for
 the backward; here it is two launches forward and three backward, and ``x`` with the per-group statistics is all that is kept.  The resize
-forms are two launches forward and four (without a skip: three) backward and keep the same.  DESIGN.md section 8e states the arithmetic."""
+forms are two launches forward and four (without a skip: three) backward and keep the same.  DESIGN.md section 8e states the arithmetic.
+
+Mixed precision: the two same-size forms also take ``x`` and ``skip`` in ``torch.bfloat16`` (together; ``weight`` and
+``bias`` stay fp32) and return bf16 -- the fp32 result on the upcast input, rounded once, bit for bit, with ``dx`` / ``dskip`` in bf16 and
+``dweight`` / ``dbias`` in fp32; the node keeps the bf16 ``x``.  Under ``torch.autocast('cuda', dtype=torch.bfloat16)`` a bf16 ``x`` stays bf16
+and ``skip`` and the parameters are cast as needed; the resize forms proper run in fp32 there.  fp16 is refused as before."""
 from __future__ import annotations
 
 import torch
@@ -26,7 +31,7 @@ _sg = torch.ops.sgrender
 
 
 def group_norm_relu(x, weight, bias, num_groups: int, eps: float = 1e-5):
-    """``relu(F.group_norm(x, num_groups, weight, bias, eps))`` for fp32 ``x [B,C,H,W]`` on a HIP device, ``weight`` / ``bias [C]``,
+    """``relu(F.group_norm(x, num_groups, weight, bias, eps))`` for fp32 or bf16 ``x [B,C,H,W]`` on a HIP device, fp32 ``weight`` / ``bias [C]``,
     ``C % num_groups == 0``.  ``x`` may be non-contiguous (a channels-last convolution output is read in place); the result is contiguous.
     Differentiable with respect to ``x``, ``weight`` and ``bias``; a gradient is computed only for those that require it.  A CPU tensor
     raises: there is no fallback."""
@@ -35,7 +40,7 @@ def group_norm_relu(x, weight, bias, num_groups: int, eps: float = 1e-5):
 
 def group_norm_relu_upcat(x, weight, bias, num_groups: int, skip, eps: float = 1e-5):
     """``F.interpolate(torch.cat([group_norm_relu(x, ...), skip], 1), scale_factor=2, mode='bilinear')``: ``[B, C + Cs, 2H, 2W]`` from
-    ``x [B,C,H,W]`` and ``skip [B,Cs,H,W]``, ``Cs >= 1``, both fp32 on a HIP device and possibly non-contiguous.  Differentiable with respect
+    ``x [B,C,H,W]`` and ``skip [B,Cs,H,W]``, ``Cs >= 1``, both fp32 or both bf16 on a HIP device and possibly non-contiguous.  Differentiable with respect
     to ``x``, ``weight``, ``bias`` and ``skip``.
 
     A ``skip`` of another ``H, W`` raises: the reference resizes the normalised map first in that case (models.py:165-166 and its

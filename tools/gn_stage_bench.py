@@ -4,6 +4,8 @@ at batch 16, forward and forward + backward.
 
     python tools/gn_stage_bench.py [--reps 80] [--warmup 10] [--out FILE.json]
     rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --profile     # the fused calls only, few repetitions
+    python tools/gn_stage_bench.py --dtype bf16 [--out FILE.json]                        # mixed precision, see below
+    rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --dtype bf16 --profile
 
 At 240x320 ``decoder0``'s second stage works at 14x20 against a 15x20 skip: the reference's resize branch.  ``dec_dgn2_plain`` times the plain
 form there (GroupNorm + ReLU alone, as before the resize was fused); ``dec_dgn2``, ``light_dgn2``, ``light_dgn3`` and ``dec_final`` are the real
@@ -13,7 +15,14 @@ Method: device events around each call, warm-up, median of >= 80, the fused call
 min-max spread of the repetitions is printed beside each median.  The algorithmic byte counts come from the shapes:
 forward reads x twice (moments, apply) and the skip once and writes the result; backward reads the cotangent and x, writes and re-reads
 the masked adjoint (upsampling form only), reads x again (plain form: the cotangent again) and writes dx and dskip.  Each fused time is
-shown with the share of that floor at 8 TB/s (the HBM peak)."""
+shown with the share of that floor at 8 TB/s (the HBM peak).
+
+``--dtype bf16`` takes the same-size stages of the list and alternates three candidates in one process: the bf16
+operator; the fp32 operator on the same values; the eager composition under ``torch.autocast('cuda', dtype=torch.bfloat16)`` reading the
+same bf16 ``x`` and ``skip`` (autocast runs ``group_norm`` in fp32: it upcasts first).  The algorithmic bytes of the bf16 operator are half
+the fp32 stage's, as every tensor it reads and writes is; the masked adjoint that the upsampling backward writes and re-reads stays fp32, so
+that form's true floor is a little higher and the printed share understates it.  Every ratio is printed against both other candidates; where the bf16 operator is slower or the spreads overlap the line says
+so in capitals."""
 import argparse
 import json
 import os
@@ -80,16 +89,89 @@ def timed(fns, reps, warm):
     return {k: sorted(v) for k, v in t.items()}
 
 
+def main_bf16(args, sgr):
+    """the same-size stages in bf16: the bf16 operator, the fp32 operator on the same values, eager under autocast on the same bf16 x"""
+    reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
+    rec = {"device": torch.cuda.get_device_name(0), "reps": reps, "batch": B, "dtype": "bf16", "ms": {}, "bytes": {}}
+    bf = torch.bfloat16
+    for name, C, G, H, W, Cs, *rest in STAGES:
+        if rest:
+            continue      # the resize forms have no bf16 kernels (DESIGN.md section 8j, "what is left")
+        g = torch.Generator().manual_seed(len(name) + C)
+        x = torch.randn(B, C, H, W, generator=g).cuda().to(bf).requires_grad_(True)
+        w = torch.randn(C, generator=g).cuda().requires_grad_(True)
+        b = (0.3 * torch.randn(C, generator=g)).cuda().requires_grad_(True)
+        skip = torch.randn(B, Cs, H, W, generator=g).cuda().to(bf).requires_grad_(True) if Cs else None
+        ct = (torch.randn(B, C + Cs, 2 * H, 2 * W, generator=g) if Cs else torch.randn(B, C, H, W, generator=g)).cuda().to(bf)
+        x32, ct32 = x.detach().float().requires_grad_(True), ct.float()
+        skip32 = skip.detach().float().requires_grad_(True) if Cs else None
+        stage = lambda x_, s_: sgr.group_norm_relu_upcat(x_, w, b, G, s_) if Cs else sgr.group_norm_relu(x_, w, b, G)
+
+        def eager():
+            with torch.autocast("cuda", dtype=bf):
+                return eager_stage(x, w, b, G, skip)
+        cands = dict(bf16=(lambda: stage(x, skip), [t for t in (x, w, b, skip) if t is not None], ct),
+                     fp32=(lambda: stage(x32, skip32), [t for t in (x32, w, b, skip32) if t is not None], ct32),
+                     eager_amp=(eager, [t for t in (x, w, b, skip) if t is not None], None))
+        out_dtype = torch.float32      # autocast's group_norm, relu, cat and interpolate run in fp32 and return fp32
+        if not args.profile:
+            assert eager().dtype == out_dtype
+        fns = {}
+        for k, (f, leaves, c) in cands.items():
+            if args.profile and k != "bf16":
+                continue
+            c = ct.to(out_dtype) if c is None else c
+
+            def fwd(f=f):
+                with torch.no_grad():
+                    return f()
+            fns[f"{k}_fwd"] = fwd
+            fns[f"{k}_fwd_bwd"] = lambda f=f, leaves=leaves, c=c: torch.autograd.grad(f(), leaves, grad_outputs=c)
+        t = timed(fns, reps, warm)
+        b_fwd, b_bwd = (v // 2 for v in nbytes(C, H, W, Cs))
+        rec["bytes"][name] = dict(forward=b_fwd, backward=b_bwd)
+        for k, v in t.items():
+            med = statistics.median(v)
+            rec["ms"][f"{name}_{k}"] = dict(median=med, min=v[0], max=v[-1])
+            note = ""
+            if k.startswith("bf16"):
+                nb = b_fwd if k == "bf16_fwd" else b_fwd + b_bwd
+                floor = nb / (HBM_TBPS * 1e12) * 1e6
+                note = f"algorithmic {nb / 1e6:.1f} MB (half the fp32 stage's): floor {floor:.1f} us at {HBM_TBPS} TB/s (share {floor / (med * 1e3):.2f})"
+            print(f"{name + '_' + k:32s} median {med * 1e3:9.1f} us  min {v[0] * 1e3:9.1f}  max {v[-1] * 1e3:9.1f}  {note}")
+        if not args.profile:
+            for k in ("fwd", "fwd_bwd"):
+                ours = rec["ms"][f"{name}_bf16_{k}"]
+                for other in ("fp32", "eager_amp"):
+                    o = rec["ms"][f"{name}_{other}_{k}"]
+                    s = o["median"] / ours["median"]
+                    rec["ms"][f"{name}_{other}_over_bf16_{k}"] = s
+                    if s >= 1:
+                        verdict = "the difference exceeds the spread" if o["min"] > ours["max"] else "THE SPREADS OVERLAP"
+                    else:
+                        verdict = "BF16 IS SLOWER" + ("" if ours["min"] > o["max"] else ", the spreads overlap")
+                    print(f"{name + '_' + k:32s} {other} / bf16 = {s:.2f}x  ({verdict})")
+        del x, w, b, skip, ct, x32, ct32, skip32, cands, fns
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=80)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     args = ap.parse_args()
     import inverserenderingofindoorscene_amd as sgr
     if not torch.cuda.is_available():
         raise SystemExit("gn_stage_bench needs a GPU")
+    if args.dtype == "bf16":
+        return main_bf16(args, sgr)
     reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
     rec = {"device": torch.cuda.get_device_name(0), "reps": reps, "batch": B, "ms": {}, "bytes": {}}
     for name, C, G, H, W, Cs, *rest in STAGES:
