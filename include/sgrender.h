@@ -588,6 +588,53 @@ int sgr_gn_resize_bwd(const float* g, const float* x, const float* weight, const
                       float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
                       const long long* x_strides, void* stream);
 
+/* ---- The upsampling stage for D sibling decoders at once: the reference runs four decoder0 and three decoderLight
+ * instances on the same encoder features, so at a stage every sibling has the same shapes and the same skip.  1 <= D <= SGR_GN_MAX_SIBLINGS.
+ * xs, weights, biases, outs, gs, dxs, dweights, dbiases: host arrays of D device pointers, read during the call (no device-side table,
+ * no copy: the calls capture in a HIP graph).  x_strides: D x 4 element strides, sibling after sibling.  stats [D,B,G,4].  skip is required.
+ *   outs[d], stats[d]              the bits of sgr_gn_stage_fwd / sgr_gn_resize_fwd for (xs[d], weights[d], biases[d], skip)
+ *   dxs[d], dweights[d], dbiases[d]  the bits of the single backward for gs[d]
+ *   dskip                          ((s_0 + s_1) + s_2) + ..., fp32, in sibling order, s_d the single backward's dskip for gs[d] as it
+ *                                  stands in registers (the bf16 form rounds the sum once); with D == 1 the single backward's bits
+ * gs[d] == NULL: sibling d has no cotangent -- it is left out of the sum and gets no dx / dweight / dbias.  A NULL array of gradients, or a
+ * NULL entry, is not wanted.  Forward: two launches for all D; backward: at most three (resize: four); no atomics, bit-identical runs,
+ * image b independent of the rest of the batch, the same bits for every layout of xs[d] and skip.  D C + Cs and D G at most 65535.
+ * Workspace: D blocks of the single operator's size (rounded up to 16 bytes), 16-byte aligned for 128-bit accesses, 8-byte at least. */
+#define SGR_GN_MAX_SIBLINGS 8
+
+long long sgr_gn_stage_siblings_workspace_floats(int D, int B, int C, int G, int H, int W, int backward);
+
+int sgr_gn_stage_siblings_fwd(int D, const float* const* xs, const float* const* weights, const float* const* biases, const float* skip,
+                              float* const* outs, float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W,
+                              const long long* x_strides, const long long* skip_strides, float eps, void* stream);
+
+int sgr_gn_stage_siblings_bwd(int D, const float* const* gs, const float* const* xs, const float* const* weights, const float* const* biases,
+                              const float* stats, float* const* dxs, float* const* dweights, float* const* dbiases, float* dskip,
+                              float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, void* stream);
+
+/* bf16 I/O as sgr_gn_stage_fwd_bf16 / _bwd_bf16: xs, skip, outs, gs, dxs and dskip in bfloat16 */
+int sgr_gn_stage_siblings_fwd_bf16(int D, const unsigned short* const* xs, const float* const* weights, const float* const* biases,
+                                   const unsigned short* skip, unsigned short* const* outs, float* stats, float* workspace, int B, int C,
+                                   int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps,
+                                   void* stream);
+
+int sgr_gn_stage_siblings_bwd_bf16(int D, const unsigned short* const* gs, const unsigned short* const* xs, const float* const* weights,
+                                   const float* const* biases, const float* stats, unsigned short* const* dxs, float* const* dweights,
+                                   float* const* dbiases, unsigned short* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W,
+                                   const long long* x_strides, void* stream);
+
+/* the resize-to-skip form (fp32 only, as sgr_gn_resize_*): skip [B,Cs,Hs,Ws], outs[d] [B,C+Cs,2Hs,2Ws] */
+long long sgr_gn_resize_siblings_workspace_floats(int D, int B, int C, int G, int H, int W, int Hs, int Ws, int backward);
+
+int sgr_gn_resize_siblings_fwd(int D, const float* const* xs, const float* const* weights, const float* const* biases, const float* skip,
+                               float* const* outs, float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
+                               const long long* x_strides, const long long* skip_strides, float eps, void* stream);
+
+int sgr_gn_resize_siblings_bwd(int D, const float* const* gs, const float* const* xs, const float* const* weights, const float* const* biases,
+                               const float* stats, float* const* dxs, float* const* dweights, float* const* dbiases, float* dskip,
+                               float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides,
+                               void* stream);
+
 /* The statistics of sgr_gn_stage_fwd without its apply pass: stats [B,G,4] of x [B,C,H,W] (read through x_strides), the same bits
  * sgr_gn_stage_fwd writes.  workspace: sgr_gn_stage_workspace_floats(B, C, G, H, W, 0, 0) floats, 8-byte aligned.  Two launches. */
 int sgr_gn_moments(const float* x, float* stats, float* workspace, int B, int C, int G, int H, int W, const long long* x_strides, float eps,

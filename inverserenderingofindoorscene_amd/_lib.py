@@ -107,6 +107,15 @@ SIGNATURES = {
     "sgr_gn_resize_workspace_floats": ([_I] * 9, c_longlong),
     "sgr_gn_resize_fwd": ([_P] * 7 + [_I] * 8 + [_P, _P, _F, _P], c_int),
     "sgr_gn_resize_bwd": ([_P] * 10 + [_I] * 8 + [_P, _P], c_int),
+    # the sibling forms: D first, then arrays of D pointers where the single forms take one
+    "sgr_gn_stage_siblings_workspace_floats": ([_I] * 7, c_longlong),
+    "sgr_gn_stage_siblings_fwd": ([_I] + [_P] * 7 + [_I] * 6 + [_P, _P, _F, _P], c_int),
+    "sgr_gn_stage_siblings_bwd": ([_I] + [_P] * 10 + [_I] * 6 + [_P, _P], c_int),
+    "sgr_gn_stage_siblings_fwd_bf16": ([_I] + [_P] * 7 + [_I] * 6 + [_P, _P, _F, _P], c_int),
+    "sgr_gn_stage_siblings_bwd_bf16": ([_I] + [_P] * 10 + [_I] * 6 + [_P, _P], c_int),
+    "sgr_gn_resize_siblings_workspace_floats": ([_I] * 9, c_longlong),
+    "sgr_gn_resize_siblings_fwd": ([_I] + [_P] * 7 + [_I] * 8 + [_P, _P, _F, _P], c_int),
+    "sgr_gn_resize_siblings_bwd": ([_I] + [_P] * 10 + [_I] * 8 + [_P, _P], c_int),
     "sgr_gn_moments": ([_P] * 3 + [_I] * 5 + [_P, _F, _P], c_int),
     "sgr_final_conv_workspace_floats": ([_I] * 5, c_longlong),
     "sgr_final_conv_fwd": ([_P] * 7 + [_I] * 6 + [_P, _P], c_int),

@@ -4,6 +4,9 @@
 //   resize  the same two with relu(group_norm(x)) resized to [Hs, Ws] first, H <= Hs <= 2H, W <= Ws <= 2W: the decoders' stage against a
 //           skip of another size and the final stage's resize to the image (:165-166 and its siblings, :185-186, :312-333); second half
 //           of this file, entry points sgr_gn_resize_*
+//   siblings  the upcat and resize forms for D <= 8 decoders that share their shapes and their skip, in the launches of one (the reference
+//           runs four decoder0 and three decoderLight instances on the same features): end of this file, entry points
+//           sgr_gn_stage_siblings_* / sgr_gn_resize_siblings_*, DESIGN.md section 8k
 // DESIGN.md section 8e states the contract; the per-element arithmetic is sgr_gn_stage.h.
 //
 // Forward, two launches: the moments of every (b, g) as double-precision (sum, sum of squares) partials, one per slice of the group, then
@@ -89,11 +92,13 @@ static long long gn_slice_len(long long n) {
 
 // partials[(b G + g) S + s] = (sum, sum of squares) over the logical elements [s L, (s+1) L) of the group; thread t takes the runs of four
 // at s L + 4 (k T + t), k = 0, 1, ..
+// The kernels below are bodies (`*_body`: the work of one workgroup, its channel or group and its image given by the caller) and the
+// `__global__` functions that place them on a grid: one per operator here, one per set of sibling operators at the end of the file.
 template <bool VEC, typename T>
-__global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const T* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W,
-                                                               int HW, long long L) {
+__device__ __forceinline__ void gn_moments_body(const T* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W, int HW, long long L,
+                                                int g, int b, int G) {
   __shared__ double lds[2 * kGThreads / 64];
-  const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z, G = gridDim.y, S = gridDim.x;
+  const int s = blockIdx.x, S = gridDim.x;
   const long long n = (long long)cpg * HW;
   const long long e0 = (long long)s * L, e1 = e0 + L < n ? e0 + L : n;
   const T* xb = x + (long long)b * xs.b + (long long)g * cpg * xs.c;
@@ -128,6 +133,11 @@ __global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const T* __restri
     o[0] = sum;
     o[1] = sq;
   }
+}
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_moments_kernel(const T* __restrict__ x, GnStrides xs, double* __restrict__ partials, int cpg, int W,
+                                                               int HW, long long L) {
+  gn_moments_body<VEC>(x, xs, partials, cpg, W, HW, L, blockIdx.y, blockIdx.z, gridDim.y);
 }
 
 // the statistics of group (b, g) from its S <= 64 partials, by the first wave: lane s holds slice s, the lanes are added by wave_sum's tree
@@ -200,13 +210,27 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_plain_kernel(const T* __re
 
 // upcat form: channel ch < C is normalised x, ch >= C is skip as it is.  A thread at (i, jj) reads source rows i-1 .. i+1 x columns
 // 2jj-1 .. 2jj+2 (clamped) and writes output rows 2i, 2i+1 x columns 4jj .. 4jj+3.  VEC: one store per run of four (W even, a result aligned for st4).
+// two output rows of four columns at o0 (row length OW; jj: the thread's column position)
 template <bool VEC, typename T>
-__global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const T* __restrict__ x, GnStrides xs, const T* __restrict__ skip, GnStrides ss,
-                                                                const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                const double* __restrict__ partials, float* __restrict__ stats,
-                                                                T* __restrict__ out, int C, int Cs, int cpg, int H, int W, int S, float eps) {
+__device__ __forceinline__ void up_store(T* __restrict__ o0, int jj, int OW, const float (&top)[4], const float (&bot)[4]) {
+  if (VEC) {
+    st4(o0, top);
+    st4(o0 + OW, bot);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (4 * jj + k < OW) { o0[k] = gn_out<T>(top[k]); o0[OW + k] = gn_out<T>(bot[k]); }
+  }
+}
+
+// store(o, jj, top, bot): writes the two rows at element o of the result -- of one result here, of every sibling's for a skip channel of
+// the sibling form
+template <bool VEC, typename T, typename Store>
+__device__ __forceinline__ void gn_apply_up_body(const T* __restrict__ x, GnStrides xs, const T* __restrict__ skip, GnStrides ss,
+                                                 const float* __restrict__ weight, const float* __restrict__ bias, const double* __restrict__ partials,
+                                                 float* __restrict__ stats, Store store, int C, int Cs, int cpg, int H, int W, int S, float eps, int ch,
+                                                 int b) {
   __shared__ float sh[4];
-  const int ch = blockIdx.y, b = blockIdx.z;
   const bool norm = ch < C;      // uniform in the workgroup
   float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
   const T* src;
@@ -227,7 +251,7 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const T* __restr
     st = ss;
   }
   const int W2 = (W + 1) >> 1, OW = 2 * W;
-  T* op = out + ((long long)b * (C + Cs) + ch) * 4ll * H * W;
+  const long long op = ((long long)b * (C + Cs) + ch) * 4ll * H * W;
   const unsigned sth = (unsigned)st.h, stw = (unsigned)st.w;      // in-plane offsets fit 31 bits (checked on the host)
   const UpTaps taps = up_taps();
   // the position (i, jj) of round 0 by one division, of the later rounds by steps of 256
@@ -250,19 +274,21 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const T* __restr
     const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
     float top[4], bot[4];
     up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top, bot);
-    T* o0 = op + (long long)(2 * i) * OW + 4 * jj;
-    if (VEC) {
-      st4(o0, top);
-      st4(o0 + OW, bot);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (4 * jj + k < OW) { o0[k] = gn_out<T>(top[k]); o0[OW + k] = gn_out<T>(bot[k]); }
-    }
+    store(op + (long long)(2 * i) * OW + 4 * jj, jj, top, bot);
     i += di;
     jj += dj;
     if (jj >= W2) { jj -= W2; ++i; }
   }
+}
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_apply_up_kernel(const T* __restrict__ x, GnStrides xs, const T* __restrict__ skip, GnStrides ss,
+                                                                const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                const double* __restrict__ partials, float* __restrict__ stats,
+                                                                T* __restrict__ out, int C, int Cs, int cpg, int H, int W, int S, float eps) {
+  const int OW = 2 * W;
+  gn_apply_up_body<VEC>(x, xs, skip, ss, weight, bias, partials, stats,
+                        [&](long long o, int jj, const float (&top)[4], const float (&bot)[4]) { up_store<VEC>(out + o, jj, OW, top, bot); }, C, Cs, cpg, H, W,
+                        S, eps, blockIdx.y, blockIdx.z);
 }
 
 // The upsample's adjoint at the source pixels (i, 2jj) and (i, 2jj+1) of an H x W plane: gp is the cotangent's plane [2H, 2W], the six weight
@@ -304,13 +330,14 @@ __device__ __forceinline__ void up_gather(const T* __restrict__ gp, int i, int j
 // Backward pass 1 over the channels [c_begin, c_begin + gridDim.y) of cat([y, skip]).  UP: g is [B,C+Cs,2H,2W] and the adjoint is gathered;
 // otherwise g is [B,C,H,W] and taken as it is.  ch < C: dy = (y > 0) adjoint, stored to `dy` (if given) and summed; ch >= C: dskip = adjoint.
 // The cotangent, x and dskip have the I/O type T; `dy` is workspace and stays fp32 (the unrounded masked adjoint, as in the fp32 operator).
-template <bool VEC, bool UP, typename T>
-__global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __restrict__ g, const T* __restrict__ x, GnStrides xs,
-                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                 const float* __restrict__ stats, float* __restrict__ dy, T* __restrict__ dskip,
-                                                                 double* __restrict__ partials, int C, int Cs, int cpg, int H, int W, int c_begin) {
+// adjoint(i, jj, a0, a1): the cotangent's adjoint at the source pixels (i, 2jj) and (i, 2jj+1) of channel ch of image b -- of one cotangent
+// here, the ordered sum over the siblings' for a skip channel of the sibling form
+template <typename T, typename Adjoint>
+__device__ __forceinline__ void gn_bwd_pass1_body(Adjoint adjoint, const T* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+                                                  const float* __restrict__ bias, const float* __restrict__ stats, float* __restrict__ dy,
+                                                  T* __restrict__ dskip, double* __restrict__ partials, int C, int Cs, int cpg, int H, int W, int ch, int b) {
   __shared__ double lds[2 * kGThreads / 64];
-  const int ch = c_begin + blockIdx.y, b = blockIdx.z, P = gridDim.x;
+  const int P = gridDim.x;
   const bool norm = ch < C;
   float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
   const T* xp = nullptr;
@@ -320,14 +347,11 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __rest
     wc = weight[ch]; bc = bias[ch];
     xp = x + (long long)b * xs.b + (long long)ch * xs.c;
   }
-  const int W2 = (W + 1) >> 1, OW = UP ? 2 * W : W, OH = UP ? 2 * H : H;
-  const T* gp = g + ((long long)b * (C + Cs) + ch) * (long long)OH * OW;
+  const int W2 = (W + 1) >> 1;
   float* dyp = norm && dy ? dy + ((long long)b * C + ch) * H * W : nullptr;
   T* dsp = norm ? nullptr : dskip + ((long long)b * Cs + (ch - C)) * H * W;
   double s1 = 0.0, s2 = 0.0;
   const unsigned sh = (unsigned)xs.h, sw = (unsigned)xs.w;      // in-plane offsets fit 31 bits (checked on the host)
-  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];      // the adjoint weights at the low edge, inside and at the high edge of either axis
-  if (UP) { up_adj_sets(H, rl, rm, rh); up_adj_sets(W, cl, cm, chi); }
   const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
   int i = q0 / W2, jj = q0 - i * W2;
 #pragma unroll 1
@@ -335,12 +359,7 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __rest
     const int c0 = 2 * jj;
     const bool two = c0 + 1 < W;
     float a0, a1;
-    if (UP) {
-      up_gather<VEC>(gp, i, jj, H, W, rl, rm, rh, cl, cm, chi, a0, a1);
-    } else {
-      a0 = gn_in(gp[(long long)i * W + c0]);
-      a1 = two ? gn_in(gp[(long long)i * W + c0 + 1]) : 0.0f;
-    }
+    adjoint(i, jj, a0, a1);
     if (norm) {
       const float x0 = gn_in(xp[(unsigned)i * sh + (unsigned)c0 * sw]);
       const float x1 = two ? gn_in(xp[(unsigned)i * sh + (unsigned)(c0 + 1) * sw]) : 0.0f;
@@ -372,12 +391,32 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __rest
     }
   }
 }
+template <bool VEC, bool UP, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass1_kernel(const T* __restrict__ g, const T* __restrict__ x, GnStrides xs,
+                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                 const float* __restrict__ stats, float* __restrict__ dy, T* __restrict__ dskip,
+                                                                 double* __restrict__ partials, int C, int Cs, int cpg, int H, int W, int c_begin) {
+  const int ch = c_begin + blockIdx.y, b = blockIdx.z;
+  const int OW = UP ? 2 * W : W, OH = UP ? 2 * H : H;
+  const T* gp = g + ((long long)b * (C + Cs) + ch) * (long long)OH * OW;
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];      // the adjoint weights at the low edge, inside and at the high edge of either axis
+  if (UP) { up_adj_sets(H, rl, rm, rh); up_adj_sets(W, cl, cm, chi); }
+  gn_bwd_pass1_body(
+      [&](int i, int jj, float& a0, float& a1) {
+        if (UP) {
+          up_gather<VEC>(gp, i, jj, H, W, rl, rm, rh, cl, cm, chi, a0, a1);
+        } else {
+          a0 = gn_in(gp[(long long)i * W + 2 * jj]);
+          a1 = 2 * jj + 1 < W ? gn_in(gp[(long long)i * W + 2 * jj + 1]) : 0.0f;
+        }
+      },
+      x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, ch, b);
+}
 
 // One wave per job.  Jobs [0, B G): (c1, c2) of group (b, g) = sum over its channels and slices of w_c (s1, s2), over n.  Jobs
 // [B G, B G + C): dweight_c = sum over b and slices of s2, dbias_c of s1.  Lane l takes the entries l, l + 64, .. in order.
-__global__ __launch_bounds__(64) void gn_bwd_fold_kernel(const double* __restrict__ partials, const float* __restrict__ weight, float* __restrict__ coef,
-                                                         float* __restrict__ dweight, float* __restrict__ dbias, int B, int C, int cpg, int P,
-                                                         double n) {
+__device__ __forceinline__ void gn_bwd_fold_body(const double* __restrict__ partials, const float* __restrict__ weight, float* __restrict__ coef,
+                                                 float* __restrict__ dweight, float* __restrict__ dbias, int B, int C, int cpg, int P, double n) {
   const int G = C / cpg, job = blockIdx.x, lane = threadIdx.x;
   double a = 0.0, q = 0.0;
   if (job < B * G) {
@@ -410,15 +449,19 @@ __global__ __launch_bounds__(64) void gn_bwd_fold_kernel(const double* __restric
     }
   }
 }
+__global__ __launch_bounds__(64) void gn_bwd_fold_kernel(const double* __restrict__ partials, const float* __restrict__ weight, float* __restrict__ coef,
+                                                         float* __restrict__ dweight, float* __restrict__ dbias, int B, int C, int cpg, int P,
+                                                         double n) {
+  gn_bwd_fold_body(partials, weight, coef, dweight, dbias, B, C, cpg, P, n);
+}
 
 // dx from dy (MASK = false: pass 1's masked adjoint) or from the cotangent itself (MASK = true: the plain form, masked here)
 // x and dx have the I/O type T; dy has TD: float for pass 1's workspace, T for the cotangent
 template <bool VEC, bool MASK, typename T, typename TD>
-__global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const TD* __restrict__ dy, const T* __restrict__ x, GnStrides xs,
-                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                 const float* __restrict__ stats, const float* __restrict__ coef,
-                                                                 T* __restrict__ dx, int C, int cpg, int W, int HW) {
-  const int c = blockIdx.y, b = blockIdx.z, G = C / cpg, g = c / cpg;
+__device__ __forceinline__ void gn_bwd_pass2_body(const TD* __restrict__ dy, const T* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+                                                  const float* __restrict__ bias, const float* __restrict__ stats, const float* __restrict__ coef,
+                                                  T* __restrict__ dx, int C, int cpg, int W, int HW, int c, int b) {
+  const int G = C / cpg, g = c / cpg;
   const float* st = stats + 4 * ((long long)b * G + g);
   const float mh = st[0], ml = st[1], rstd = st[2], wc = weight[c], bc = bias[c];
   const float c1 = coef[2 * (b * G + g)], c2 = coef[2 * (b * G + g) + 1];
@@ -456,6 +499,13 @@ __global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const TD* __res
     }
   }
 }
+template <bool VEC, bool MASK, typename T, typename TD>
+__global__ __launch_bounds__(kGThreads) void gn_bwd_pass2_kernel(const TD* __restrict__ dy, const T* __restrict__ x, GnStrides xs,
+                                                                 const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                 const float* __restrict__ stats, const float* __restrict__ coef,
+                                                                 T* __restrict__ dx, int C, int cpg, int W, int HW) {
+  gn_bwd_pass2_body<VEC, MASK>(dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW, blockIdx.y, blockIdx.z);
+}
 
 // ---- the resize-to-skip forms (models.py:165-166 and its siblings; 185-186): y is resized from H x W to the skip's Hs x Ws before the
 // concatenation, H <= Hs <= 2H and W <= Ws <= 2W.  The arithmetic is the rs_* part of sgr_gn_stage.h; sch / scw are the fp32 scales
@@ -473,14 +523,13 @@ __device__ __forceinline__ float rs_gn_value(const float* __restrict__ src, unsi
 }
 
 // resize + upcat: gn_apply_up_kernel at the skip's resolution, the 3 x 4 neighbourhood of a normalised channel formed from x on the fly
-template <bool VEC, bool SAMEW>
-__global__ __launch_bounds__(kGThreads) void gn_apply_rsup_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
-                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                  const double* __restrict__ partials, float* __restrict__ stats,
-                                                                  float* __restrict__ out, int C, int Cs, int cpg, int H, int W, int Hs, int Ws,
-                                                                  float sch, float scw, int S, float eps) {
+// (store: as gn_apply_up_body's)
+template <bool SAMEW, typename Store>
+__device__ __forceinline__ void gn_apply_rsup_body(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
+                                                   const float* __restrict__ weight, const float* __restrict__ bias, const double* __restrict__ partials,
+                                                   float* __restrict__ stats, Store store, int C, int Cs, int cpg, int H, int W, int Hs, int Ws, float sch,
+                                                   float scw, int S, float eps, int ch, int b) {
   __shared__ float sh[4];
-  const int ch = blockIdx.y, b = blockIdx.z;
   const bool norm = ch < C;      // uniform in the workgroup
   float mh = 0.0f, ml = 0.0f, rstd = 1.0f, wc = 1.0f, bc = 0.0f;
   const float* src;
@@ -501,7 +550,7 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_rsup_kernel(const float* _
     st = ss;
   }
   const int W2 = (Ws + 1) >> 1, OW = 2 * Ws;
-  float* op = out + ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
+  const long long op = ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
   const unsigned sth = (unsigned)st.h, stw = (unsigned)st.w;      // in-plane offsets fit 31 bits (checked on the host)
   const UpTaps taps = up_taps();
   const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
@@ -529,21 +578,24 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_rsup_kernel(const float* _
         for (int k = 0; k < 4; ++k) v[a][k] = src[(unsigned)rr[a] * sth + (unsigned)cc[k] * stw];
     }
     const UpTap tc[4] = {up_pick(taps, 4 * jj), taps.odd, taps.even, taps.odd};
-    Vec<4> top, bot;
-    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top.v, bot.v);
-    float* o0 = op + (long long)(2 * i) * OW + 4 * jj;
-    if (VEC) {
-      *reinterpret_cast<Vec<4>*>(o0) = top;
-      *reinterpret_cast<Vec<4>*>(o0 + OW) = bot;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (4 * jj + k < OW) { o0[k] = top.v[k]; o0[OW + k] = bot.v[k]; }
-    }
+    float top[4], bot[4];
+    up_quad(v, tc, up_pick(taps, 2 * i), taps.odd, top, bot);
+    store(op + (long long)(2 * i) * OW + 4 * jj, jj, top, bot);
     i += di;
     jj += dj;
     if (jj >= W2) { jj -= W2; ++i; }
   }
+}
+template <bool VEC, bool SAMEW>
+__global__ __launch_bounds__(kGThreads) void gn_apply_rsup_kernel(const float* __restrict__ x, GnStrides xs, const float* __restrict__ skip, GnStrides ss,
+                                                                  const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                  const double* __restrict__ partials, float* __restrict__ stats,
+                                                                  float* __restrict__ out, int C, int Cs, int cpg, int H, int W, int Hs, int Ws,
+                                                                  float sch, float scw, int S, float eps) {
+  const int OW = 2 * Ws;
+  gn_apply_rsup_body<SAMEW>(x, xs, skip, ss, weight, bias, partials, stats,
+                            [&](long long o, int jj, const float (&top)[4], const float (&bot)[4]) { up_store<VEC>(out + o, jj, OW, top, bot); }, C, Cs, cpg,
+                            H, W, Hs, Ws, sch, scw, S, eps, blockIdx.y, blockIdx.z);
 }
 
 // resize alone (the final stage): a thread makes the columns 4jq .. 4jq+3 of resized row i.  VEC: 128-bit stores (Ws % 4 == 0, aligned result).
@@ -592,22 +644,18 @@ __global__ __launch_bounds__(kGThreads) void gn_apply_rs_kernel(const float* __r
 
 // Backward, step 1 of the resize + upcat form: the upsample's adjoint at the skip's resolution, unmasked, over the channels
 // [c_begin, c_begin + gridDim.y) of the concatenation.  ch < C goes to `da` [B,C,Hs,Ws] (workspace), ch >= C is dskip.
-template <bool VEC>
-__global__ __launch_bounds__(kGThreads) void gn_up_adjoint_kernel(const float* __restrict__ g, float* __restrict__ da, float* __restrict__ dskip, int C,
-                                                                  int Cs, int Hs, int Ws, int c_begin) {
-  const int ch = c_begin + blockIdx.y, b = blockIdx.z;
+// (adjoint: as gn_bwd_pass1_body's)
+template <typename Adjoint>
+__device__ __forceinline__ void gn_up_adjoint_body(Adjoint adjoint, float* __restrict__ da, float* __restrict__ dskip, int C, int Cs, int Hs, int Ws, int ch,
+                                                   int b) {
   const int W2 = (Ws + 1) >> 1;
-  const float* gp = g + ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
   float* dst = ch < C ? da + ((long long)b * C + ch) * Hs * Ws : dskip + ((long long)b * Cs + (ch - C)) * Hs * Ws;
-  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];
-  up_adj_sets(Hs, rl, rm, rh);
-  up_adj_sets(Ws, cl, cm, chi);
   const int q0 = blockIdx.x * kGRounds * kGThreads + threadIdx.x, di = kGThreads / W2, dj = kGThreads - di * W2;
   int i = q0 / W2, jj = q0 - i * W2;
 #pragma unroll 1
   for (int r = 0; r < kGRounds && i < Hs; ++r) {
     float a0, a1;
-    up_gather<VEC>(gp, i, jj, Hs, Ws, rl, rm, rh, cl, cm, chi, a0, a1);
+    adjoint(i, jj, a0, a1);
     dst[(long long)i * Ws + 2 * jj] = a0;
     if (2 * jj + 1 < Ws) dst[(long long)i * Ws + 2 * jj + 1] = a1;
     i += di;
@@ -615,18 +663,28 @@ __global__ __launch_bounds__(kGThreads) void gn_up_adjoint_kernel(const float* _
     if (jj >= W2) { jj -= W2; ++i; }
   }
 }
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_up_adjoint_kernel(const float* __restrict__ g, float* __restrict__ da, float* __restrict__ dskip, int C,
+                                                                  int Cs, int Hs, int Ws, int c_begin) {
+  const int ch = c_begin + blockIdx.y, b = blockIdx.z;
+  const float* gp = g + ((long long)b * (C + Cs) + ch) * 4ll * Hs * Ws;
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];
+  up_adj_sets(Hs, rl, rm, rh);
+  up_adj_sets(Ws, cl, cm, chi);
+  gn_up_adjoint_body([&](int i, int jj, float& a0, float& a1) { up_gather<VEC>(gp, i, jj, Hs, Ws, rl, rm, rh, cl, cm, chi, a0, a1); }, da, dskip, C, Cs, Hs,
+                     Ws, ch, b);
+}
 
 // Backward, the resize's adjoint gathered at the source resolution, one source pixel per thread and round: a [B,C,Hs,Ws] is step 1's `da`
 // or, in the form without a skip, the cotangent itself.  dy = (y > 0) adjoint, stored (if given) and summed as gn_bwd_pass1_kernel does:
 // the fold and pass 2 that follow are the existing ones.  FC: the columns of the window (1 with W == Ws: the pixel's own column).
 template <int FC>
-__global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float* __restrict__ a, const float* __restrict__ x, GnStrides xs,
-                                                                    const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                    const float* __restrict__ stats, float* __restrict__ dy, double* __restrict__ partials,
-                                                                    int C, int cpg, int H, int W, int Hs, int Ws, float sch, float scw, float inh,
-                                                                    float inw) {
+__device__ __forceinline__ void gn_rs_bwd_pass1_body(const float* __restrict__ a, const float* __restrict__ x, GnStrides xs, const float* __restrict__ weight,
+                                                     const float* __restrict__ bias, const float* __restrict__ stats, float* __restrict__ dy,
+                                                     double* __restrict__ partials, int C, int cpg, int H, int W, int Hs, int Ws, float sch, float scw,
+                                                     float inh, float inw, int ch, int b) {
   __shared__ double lds[2 * kGThreads / 64];
-  const int ch = blockIdx.y, b = blockIdx.z, P = gridDim.x;
+  const int P = gridDim.x;
   const float* st = stats + 4 * ((long long)b * (C / cpg) + ch / cpg);
   const float mh = st[0], ml = st[1], rstd = st[2], wc = weight[ch], bc = bias[ch];
   const float* xp = x + (long long)b * xs.b + (long long)ch * xs.c;
@@ -677,6 +735,14 @@ __global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float*
     o[0] = s1;
     o[1] = s2;
   }
+}
+template <int FC>
+__global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float* __restrict__ a, const float* __restrict__ x, GnStrides xs,
+                                                                    const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                    const float* __restrict__ stats, float* __restrict__ dy, double* __restrict__ partials,
+                                                                    int C, int cpg, int H, int W, int Hs, int Ws, float sch, float scw, float inh,
+                                                                    float inw) {
+  gn_rs_bwd_pass1_body<FC>(a, x, xs, weight, bias, stats, dy, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw, blockIdx.y, blockIdx.z);
 }
 
 // the planes of t are rows of W consecutive elements, H W % 4 == 0, and every plane starts on the boundary of a run of four (16 bytes of
@@ -966,4 +1032,452 @@ extern "C" int sgr_gn_moments(const float* x, float* stats, float* workspace, in
     hipLaunchKernelGGL((gn_moments_kernel<false, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
   hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, st, partials, stats, S, (double)n, eps);
   return sgr_check((int)hipGetLastError(), "sgr_gn_moments");
+}
+
+// ---- the sibling forms: D <= 8 decoders at the same stage, one shape, one skip ----------------------------------------
+// The bodies above on a grid that carries the sibling index on its y axis: D C normalised channels (sibling d, channel c at d C + c), then
+// the Cs skip channels once.  A skip channel is read once and written into all D results (forward); in the backward its adjoint is formed
+// in registers per sibling, as the single operators form it, and added in sibling order.  The siblings' tensors and parameters travel as
+// a table in the kernel arguments; the workspace holds D blocks, each laid out as the single operator's.
+
+namespace sgr {
+
+constexpr int kGSiblings = SGR_GN_MAX_SIBLINGS;
+
+template <typename T>
+struct SibFwd {
+  const T* x[kGSiblings];
+  GnStrides xs[kGSiblings];
+  const float* weight[kGSiblings];
+  const float* bias[kGSiblings];
+  T* out[kGSiblings];
+};
+// g[d] == nullptr: sibling d has no cotangent (and then no dx / dweight / dbias either: the host clears them)
+template <typename T>
+struct SibBwd {
+  const T* g[kGSiblings];
+  const T* x[kGSiblings];
+  GnStrides xs[kGSiblings];
+  const float* weight[kGSiblings];
+  const float* bias[kGSiblings];
+  T* dx[kGSiblings];
+  float* dweight[kGSiblings];
+  float* dbias[kGSiblings];
+  __device__ bool side(int d) const { return dx[d] || dweight[d] || dbias[d]; }
+};
+// sibling d's block of the backward workspace: partials (doubles), the group coefficients, dy, then (resize) da
+struct SibWs {
+  float* base;
+  long long stride, coef, dy, da;      // floats
+  __device__ double* partials(int d) const { return reinterpret_cast<double*>(base + d * stride); }
+  __device__ float* coefs(int d) const { return base + d * stride + coef; }
+  __device__ float* dys(int d) const { return base + d * stride + dy; }
+  __device__ float* das(int d) const { return base + d * stride + da; }
+};
+
+// y of the grid -> (first sibling, one past the last sibling, channel of cat([y, skip])): a normalised channel belongs to one sibling, a
+// skip channel to all of them
+struct SibChannel { int d0, d1, ch; };
+__device__ __forceinline__ SibChannel sib_channel(int y, int C, int D) {
+  if (y < C * D) {
+    const int d = y / C;
+    return {d, d + 1, y - d * C};
+  }
+  return {0, D, C + (y - C * D)};
+}
+
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_sib_moments_kernel(SibFwd<T> t, double* __restrict__ partials, long long stride, int G, int cpg, int W, int HW,
+                                                                   long long L) {
+  const int d = blockIdx.y / G, g = blockIdx.y - d * G;
+  gn_moments_body<VEC>(t.x[d], t.xs[d], partials + d * stride, cpg, W, HW, L, g, blockIdx.z, G);
+}
+
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_sib_apply_up_kernel(SibFwd<T> t, int D, const T* __restrict__ skip, GnStrides ss,
+                                                                    const double* __restrict__ partials, long long stride, float* __restrict__ stats, int C,
+                                                                    int Cs, int cpg, int H, int W, int S, float eps) {
+  const SibChannel k = sib_channel(blockIdx.y, C, D);
+  const int OW = 2 * W, d = k.d0, BG = gridDim.z * (C / cpg);
+  gn_apply_up_body<VEC>(t.x[d], t.xs[d], skip, ss, t.weight[d], t.bias[d], partials + d * stride, stats + 4ll * d * BG,
+                        [&](long long o, int jj, const float (&top)[4], const float (&bot)[4]) {
+                          for (int e = k.d0; e < k.d1; ++e) up_store<VEC>(t.out[e] + o, jj, OW, top, bot);
+                        },
+                        C, Cs, cpg, H, W, S, eps, k.ch, blockIdx.z);
+}
+
+template <bool VEC, bool SAMEW>
+__global__ __launch_bounds__(kGThreads) void gn_sib_apply_rsup_kernel(SibFwd<float> t, int D, const float* __restrict__ skip, GnStrides ss,
+                                                                      const double* __restrict__ partials, long long stride, float* __restrict__ stats,
+                                                                      int C, int Cs, int cpg, int H, int W, int Hs, int Ws, float sch, float scw, int S,
+                                                                      float eps) {
+  const SibChannel k = sib_channel(blockIdx.y, C, D);
+  const int OW = 2 * Ws, d = k.d0, BG = gridDim.z * (C / cpg);
+  gn_apply_rsup_body<SAMEW>(t.x[d], t.xs[d], skip, ss, t.weight[d], t.bias[d], partials + d * stride, stats + 4ll * d * BG,
+                            [&](long long o, int jj, const float (&top)[4], const float (&bot)[4]) {
+                              for (int e = k.d0; e < k.d1; ++e) up_store<VEC>(t.out[e] + o, jj, OW, top, bot);
+                            },
+                            C, Cs, cpg, H, W, Hs, Ws, sch, scw, S, eps, k.ch, blockIdx.z);
+}
+
+// The upsample's adjoint of channel k.ch of image b at (i, 2jj), (i, 2jj+1) of an H x W plane: one sibling's for a normalised channel; for
+// a skip channel ((s_0 + s_1) + s_2) + ... over the siblings that have a cotangent, each s_d formed as the single operator forms it
+template <bool VEC, typename T>
+__device__ __forceinline__ void sib_adjoint(const SibBwd<T>& t, const SibChannel& k, long long plane, int i, int jj, int H, int W, const float (&rl)[4],
+                                            const float (&rm)[4], const float (&rh)[4], const float (&cl)[4], const float (&cm)[4], const float (&chi)[4],
+                                            float& a0, float& a1) {
+  bool first = true;
+  a0 = 0.0f;
+  a1 = 0.0f;
+  for (int e = k.d0; e < k.d1; ++e) {
+    const T* g = t.g[e];
+    if (!g) continue;      // uniform in the workgroup
+    float u0, u1;
+    up_gather<VEC>(g + plane, i, jj, H, W, rl, rm, rh, cl, cm, chi, u0, u1);
+    a0 = first ? u0 : a0 + u0;
+    a1 = first ? u1 : a1 + u1;
+    first = false;
+  }
+}
+
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_sib_bwd_pass1_kernel(SibBwd<T> t, int D, const float* __restrict__ stats, SibWs ws, T* __restrict__ dskip,
+                                                                     int C, int Cs, int cpg, int H, int W, int y_begin) {
+  const SibChannel k = sib_channel(y_begin + blockIdx.y, C, D);
+  const int d = k.d0, b = blockIdx.z, BG = gridDim.z * (C / cpg);
+  if (k.ch < C && !t.side(d)) return;      // a sibling without a cotangent, or with nothing wanted behind its normalisation
+  const long long plane = ((long long)b * (C + Cs) + k.ch) * 4ll * H * W;
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];
+  up_adj_sets(H, rl, rm, rh);
+  up_adj_sets(W, cl, cm, chi);
+  gn_bwd_pass1_body([&](int i, int jj, float& a0, float& a1) { sib_adjoint<VEC>(t, k, plane, i, jj, H, W, rl, rm, rh, cl, cm, chi, a0, a1); }, t.x[d], t.xs[d],
+                    t.weight[d], t.bias[d], stats + 4ll * d * BG, t.dx[d] ? ws.dys(d) : nullptr, dskip, ws.partials(d), C, Cs, cpg, H, W, k.ch, b);
+}
+
+__global__ __launch_bounds__(64) void gn_sib_bwd_fold_kernel(SibBwd<float> t, SibWs ws, int B, int C, int cpg, int P, double n) {
+  const int d = blockIdx.y;
+  if (!t.side(d)) return;
+  gn_bwd_fold_body(ws.partials(d), t.weight[d], ws.coefs(d), t.dweight[d], t.dbias[d], B, C, cpg, P, n);
+}
+
+template <bool VEC, typename T>
+__global__ __launch_bounds__(kGThreads) void gn_sib_bwd_pass2_kernel(SibBwd<T> t, const float* __restrict__ stats, SibWs ws, int C, int cpg, int W, int HW) {
+  const int d = blockIdx.y / C, c = blockIdx.y - d * C, BG = gridDim.z * (C / cpg);
+  if (!t.dx[d]) return;
+  gn_bwd_pass2_body<VEC, false, T, float>(ws.dys(d), t.x[d], t.xs[d], t.weight[d], t.bias[d], stats + 4ll * d * BG, ws.coefs(d), t.dx[d], C, cpg, W, HW, c,
+                                          blockIdx.z);
+}
+
+// resize form, step 1: the upsample's adjoint at the skip's resolution; sibling d's normalised channels go to its `da`
+template <bool VEC>
+__global__ __launch_bounds__(kGThreads) void gn_sib_up_adjoint_kernel(SibBwd<float> t, int D, SibWs ws, float* __restrict__ dskip, int C, int Cs, int Hs, int Ws,
+                                                                      int y_begin) {
+  const SibChannel k = sib_channel(y_begin + blockIdx.y, C, D);
+  const int b = blockIdx.z;
+  if (k.ch < C && !t.side(k.d0)) return;
+  const long long plane = ((long long)b * (C + Cs) + k.ch) * 4ll * Hs * Ws;
+  float rl[4], rm[4], rh[4], cl[4], cm[4], chi[4];
+  up_adj_sets(Hs, rl, rm, rh);
+  up_adj_sets(Ws, cl, cm, chi);
+  gn_up_adjoint_body([&](int i, int jj, float& a0, float& a1) { sib_adjoint<VEC>(t, k, plane, i, jj, Hs, Ws, rl, rm, rh, cl, cm, chi, a0, a1); },
+                     ws.das(k.d0), dskip, C, Cs, Hs, Ws, k.ch, b);
+}
+
+template <int FC>
+__global__ __launch_bounds__(kGThreads) void gn_sib_rs_bwd_pass1_kernel(SibBwd<float> t, const float* __restrict__ stats, SibWs ws, int C, int cpg, int H, int W,
+                                                                        int Hs, int Ws, float sch, float scw, float inh, float inw) {
+  const int d = blockIdx.y / C, ch = blockIdx.y - d * C, BG = gridDim.z * (C / cpg);
+  if (!t.side(d)) return;
+  gn_rs_bwd_pass1_body<FC>(ws.das(d), t.x[d], t.xs[d], t.weight[d], t.bias[d], stats + 4ll * d * BG, t.dx[d] ? ws.dys(d) : nullptr, ws.partials(d), C, cpg, H,
+                           W, Hs, Ws, sch, scw, inh, inw, ch, blockIdx.z);
+}
+
+// a block of the sibling workspace: the single operator's floats, rounded up so that every block starts on 16 bytes
+static long long sib_block(long long single) { return (single + 3) / 4 * 4; }
+
+#define SIB_CHECK_SIZES(who)                                                                                     \
+  SGR_REQUIRE(D >= 1 && D <= kGSiblings, who ": the number of siblings must be 1 .. 8");                          \
+  GN_CHECK_SIZES(who);                                                                                           \
+  SGR_REQUIRE(Cs > 0, who ": the sibling forms need a skip");                                                     \
+  SGR_SUPPORTED((long long)C * D + Cs <= 65535 && (long long)G * D <= 65535, who ": D * C + Cs or D * G > 65535")
+
+template <typename T>
+static bool sib_fwd_table(SibFwd<T>& t, int D, const T* const* xs, const float* const* weights, const float* const* biases, T* const* outs,
+                          const long long* x_strides, int H, int W, bool& xvec, bool& ovec) {
+  xvec = ovec = true;
+  for (int d = 0; d < kGSiblings; ++d) {
+    const int e = d < D ? d : 0;      // the unused entries repeat sibling 0: no kernel reads them
+    if (!xs[e] || !weights[e] || !biases[e] || !outs[e]) return false;
+    const long long* s = x_strides + 4 * e;
+    t.x[d] = xs[e]; t.weight[d] = weights[e]; t.bias[d] = biases[e]; t.out[d] = outs[e];
+    t.xs[d] = GnStrides{s[0], s[1], s[2], s[3]};
+    xvec = xvec && g_plane_vec(t.x[d], t.xs[d], H, W);
+    ovec = ovec && aligned_run<T>({t.out[d]});
+  }
+  return true;
+}
+static bool sib_strides_fit(int D, const long long* x_strides, int H, int W) {
+  for (int d = 0; d < D; ++d)
+    if (!g_plane_fits(x_strides + 4 * d, H, W)) return false;
+  return true;
+}
+
+template <typename T>
+static int gn_stage_siblings_fwd_t(int D, const T* const* xs, const float* const* weights, const float* const* biases, const T* skip, T* const* outs, float* stats,
+                                   float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides,
+                                   float eps, void* stream) {
+  SGR_REQUIRE(xs && weights && biases && skip && outs && stats && workspace && x_strides && skip_strides, "sgr_gn_stage_siblings_fwd: NULL tensor");
+  SIB_CHECK_SIZES("sgr_gn_stage_siblings_fwd");
+  SGR_REQUIRE(eps > 0.0f, "sgr_gn_stage_siblings_fwd: eps must be positive");
+  SGR_SUPPORTED(sib_strides_fit(D, x_strides, H, W) && g_plane_fits(skip_strides, H, W), "sgr_gn_stage_siblings_fwd: negative or out-of-range plane strides");
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_siblings_fwd: the workspace must be 8-byte aligned");
+  SibFwd<T> t;
+  bool xvec, ovec;
+  SGR_REQUIRE(sib_fwd_table(t, D, xs, weights, biases, outs, x_strides, H, W, xvec, ovec), "sgr_gn_stage_siblings_fwd: NULL tensor of a sibling");
+  const GnStrides ss{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]};
+  const int cpg = C / G, HW = H * W;
+  const long long n = (long long)cpg * HW;
+  const int S = gn_slices(n);
+  const long long stride = 2ll * B * G * S;      // doubles: the single forward's workspace
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 mgrid(S, G * D, B), mblock(n <= 2048 ? 64 : kGThreads);
+  if (xvec)
+    hipLaunchKernelGGL((gn_sib_moments_kernel<true, T>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
+  else
+    hipLaunchKernelGGL((gn_sib_moments_kernel<false, T>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
+  const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C * D + Cs, B);
+  if (W % 2 == 0 && ovec)
+    hipLaunchKernelGGL((gn_sib_apply_up_kernel<true, T>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, S, eps);
+  else
+    hipLaunchKernelGGL((gn_sib_apply_up_kernel<false, T>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, S, eps);
+  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_siblings_fwd");
+}
+
+// The backward's table: a sibling without a cotangent gets no gradient; `any` = some sibling wants dx, dweight or dbias.
+template <typename T>
+static bool sib_bwd_table(SibBwd<T>& t, int D, const T* const* gs, const T* const* xs, const float* const* weights, const float* const* biases, T* const* dxs,
+                          float* const* dweights, float* const* dbiases, const long long* x_strides, bool& any, bool& anyg, bool& anyw, bool& anydx) {
+  any = anyg = anyw = anydx = false;
+  for (int d = 0; d < kGSiblings; ++d) {
+    t.g[d] = d < D ? gs[d] : nullptr;
+    const bool has = t.g[d] != nullptr;
+    t.dx[d] = has && dxs ? dxs[d] : nullptr;
+    t.dweight[d] = has && dweights ? dweights[d] : nullptr;
+    t.dbias[d] = has && dbiases ? dbiases[d] : nullptr;
+    t.x[d] = nullptr; t.weight[d] = nullptr; t.bias[d] = nullptr;
+    t.xs[d] = GnStrides{0, 0, 0, 0};
+    anyg = anyg || has;
+    if (t.dx[d] || t.dweight[d] || t.dbias[d]) {
+      if (!xs || !weights || !biases || !x_strides || !xs[d] || !weights[d] || !biases[d]) return false;
+      const long long* s = x_strides + 4 * d;
+      t.x[d] = xs[d]; t.weight[d] = weights[d]; t.bias[d] = biases[d];
+      t.xs[d] = GnStrides{s[0], s[1], s[2], s[3]};
+      any = true;
+      anyw = anyw || t.dweight[d] || t.dbias[d];
+      anydx = anydx || t.dx[d];
+    }
+  }
+  return true;
+}
+template <typename T>
+static bool sib_bwd_strides_fit(const SibBwd<T>& t, int D, int H, int W) {
+  for (int d = 0; d < D; ++d) {
+    const long long s[4] = {t.xs[d].b, t.xs[d].c, t.xs[d].h, t.xs[d].w};
+    if (t.x[d] && !g_plane_fits(s, H, W)) return false;
+  }
+  return true;
+}
+// 128-bit (64-bit) accesses in the kernels that take them: every cotangent, or every (dy, x, dx) of the siblings that want dx
+template <typename T>
+static bool sib_g_vec(const SibBwd<T>& t, int D) {
+  for (int d = 0; d < D; ++d)
+    if (t.g[d] && !aligned_run<T>({t.g[d]})) return false;
+  return true;
+}
+template <typename T>
+static bool sib_dx_vec(const SibBwd<T>& t, int D, int H, int W) {
+  for (int d = 0; d < D; ++d)
+    if (t.dx[d] && !(g_plane_vec(t.x[d], t.xs[d], H, W) && aligned_run<T>({t.dx[d]}))) return false;
+  return true;
+}
+// the fold runs on the parameters alone: one instantiation serves both I/O types
+template <typename T>
+static SibBwd<float> sib_fold_table(const SibBwd<T>& t) {
+  SibBwd<float> f{};
+  for (int d = 0; d < kGSiblings; ++d) {
+    f.weight[d] = t.weight[d]; f.dweight[d] = t.dweight[d]; f.dbias[d] = t.dbias[d];
+    f.dx[d] = t.dx[d] ? reinterpret_cast<float*>(t.dx[d]) : nullptr;      // only tested against nullptr
+  }
+  return f;
+}
+
+template <typename T>
+static int gn_stage_siblings_bwd_t(int D, const T* const* gs, const T* const* xs, const float* const* weights, const float* const* biases, const float* stats,
+                                   T* const* dxs, float* const* dweights, float* const* dbiases, T* dskip, float* workspace, int B, int C, int G, int Cs, int H,
+                                   int W, const long long* x_strides, void* stream) {
+  SGR_REQUIRE(gs, "sgr_gn_stage_siblings_bwd: NULL cotangent");
+  SIB_CHECK_SIZES("sgr_gn_stage_siblings_bwd");
+  SibBwd<T> t;
+  bool side, anyg, anyw, anydx;
+  SGR_REQUIRE(sib_bwd_table(t, D, gs, xs, weights, biases, dxs, dweights, dbiases, x_strides, side, anyg, anyw, anydx), "sgr_gn_stage_siblings_bwd: NULL tensor");
+  SGR_REQUIRE(anyg, "sgr_gn_stage_siblings_bwd: NULL cotangent");
+  SGR_REQUIRE(side || dskip, "sgr_gn_stage_siblings_bwd: no gradient requested");
+  SGR_REQUIRE(!side || (stats && workspace), "sgr_gn_stage_siblings_bwd: NULL tensor");
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_siblings_bwd: the workspace must be 8-byte aligned");
+  SGR_SUPPORTED(sib_bwd_strides_fit(t, D, H, W), "sgr_gn_stage_siblings_bwd: negative or out-of-range plane strides");
+  const int cpg = C / G, HW = H * W, P = g_bwd_slices(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  SibWs ws;
+  ws.base = workspace;
+  ws.coef = 4ll * B * C * P;
+  ws.dy = ws.coef + g_coef_floats(B, G);
+  ws.da = 0;
+  ws.stride = sib_block(ws.dy + (long long)B * C * HW);
+  // pass 1: the channels somebody wants
+  const int y_begin = side ? 0 : C * D, y_end = dskip ? C * D + Cs : C * D;
+  const dim3 grid1(P, y_end - y_begin, B);
+  if (W % 2 == 0 && sib_g_vec(t, D))
+    hipLaunchKernelGGL((gn_sib_bwd_pass1_kernel<true, T>), grid1, dim3(kGThreads), 0, st, t, D, stats, ws, dskip, C, Cs, cpg, H, W, y_begin);
+  else
+    hipLaunchKernelGGL((gn_sib_bwd_pass1_kernel<false, T>), grid1, dim3(kGThreads), 0, st, t, D, stats, ws, dskip, C, Cs, cpg, H, W, y_begin);
+  if (side) hipLaunchKernelGGL(gn_sib_bwd_fold_kernel, dim3(B * G + (anyw ? C : 0), D), dim3(64), 0, st, sib_fold_table(t), ws, B, C, cpg, P, (double)cpg * HW);
+  if (anydx) {
+    const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C * D, B);
+    if (sib_dx_vec(t, D, H, W) && aligned16({workspace}))      // HW % 4 == 0 here: every block's dy is on 16 bytes with the workspace
+      hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<true, T>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
+    else
+      hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<false, T>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_siblings_bwd");
+}
+
+}  // namespace sgr
+
+extern "C" long long sgr_gn_stage_siblings_workspace_floats(int D, int B, int C, int G, int H, int W, int backward) {
+  if (D < 1 || D > kGSiblings) return 0;
+  const long long single = sgr_gn_stage_workspace_floats(B, C, G, H, W, 1, backward);
+  return single > 0 ? D * sib_block(single) : 0;
+}
+extern "C" int sgr_gn_stage_siblings_fwd(int D, const float* const* xs, const float* const* weights, const float* const* biases, const float* skip,
+                                         float* const* outs, float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W,
+                                         const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
+  return gn_stage_siblings_fwd_t<float>(D, xs, weights, biases, skip, outs, stats, workspace, B, C, G, Cs, H, W, x_strides, skip_strides, eps, stream);
+}
+extern "C" int sgr_gn_stage_siblings_bwd(int D, const float* const* gs, const float* const* xs, const float* const* weights, const float* const* biases,
+                                         const float* stats, float* const* dxs, float* const* dweights, float* const* dbiases, float* dskip, float* workspace,
+                                         int B, int C, int G, int Cs, int H, int W, const long long* x_strides, void* stream) {
+  return gn_stage_siblings_bwd_t<float>(D, gs, xs, weights, biases, stats, dxs, dweights, dbiases, dskip, workspace, B, C, G, Cs, H, W, x_strides, stream);
+}
+extern "C" int sgr_gn_stage_siblings_fwd_bf16(int D, const unsigned short* const* xs, const float* const* weights, const float* const* biases,
+                                              const unsigned short* skip, unsigned short* const* outs, float* stats, float* workspace, int B, int C, int G,
+                                              int Cs, int H, int W, const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
+  return gn_stage_siblings_fwd_t<bf16>(D, reinterpret_cast<const bf16* const*>(xs), weights, biases, reinterpret_cast<const bf16*>(skip),
+                                       reinterpret_cast<bf16* const*>(outs), stats, workspace, B, C, G, Cs, H, W, x_strides, skip_strides, eps, stream);
+}
+extern "C" int sgr_gn_stage_siblings_bwd_bf16(int D, const unsigned short* const* gs, const unsigned short* const* xs, const float* const* weights,
+                                              const float* const* biases, const float* stats, unsigned short* const* dxs, float* const* dweights,
+                                              float* const* dbiases, unsigned short* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W,
+                                              const long long* x_strides, void* stream) {
+  return gn_stage_siblings_bwd_t<bf16>(D, reinterpret_cast<const bf16* const*>(gs), reinterpret_cast<const bf16* const*>(xs), weights, biases, stats,
+                                       reinterpret_cast<bf16* const*>(dxs), dweights, dbiases, reinterpret_cast<bf16*>(dskip), workspace, B, C, G, Cs, H, W,
+                                       x_strides, stream);
+}
+
+extern "C" long long sgr_gn_resize_siblings_workspace_floats(int D, int B, int C, int G, int H, int W, int Hs, int Ws, int backward) {
+  if (D < 1 || D > kGSiblings) return 0;
+  const long long single = sgr_gn_resize_workspace_floats(B, C, G, H, W, Hs, Ws, 1, backward);
+  return single > 0 ? D * sib_block(single) : 0;
+}
+
+extern "C" int sgr_gn_resize_siblings_fwd(int D, const float* const* xs, const float* const* weights, const float* const* biases, const float* skip,
+                                          float* const* outs, float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
+                                          const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
+  SGR_REQUIRE(xs && weights && biases && skip && outs && stats && workspace && x_strides && skip_strides, "sgr_gn_resize_siblings_fwd: NULL tensor");
+  SIB_CHECK_SIZES("sgr_gn_resize_siblings_fwd");
+  SGR_REQUIRE(Hs > 0 && Ws > 0, "sgr_gn_resize_siblings_fwd: non-positive size");
+  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), "sgr_gn_resize_siblings_fwd: outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");
+  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), "sgr_gn_resize_siblings_fwd: Hs * Ws out of range");
+  SGR_REQUIRE(eps > 0.0f, "sgr_gn_resize_siblings_fwd: eps must be positive");
+  SGR_SUPPORTED(sib_strides_fit(D, x_strides, H, W) && g_plane_fits(skip_strides, Hs, Ws), "sgr_gn_resize_siblings_fwd: negative or out-of-range plane strides");
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_siblings_fwd: the workspace must be 8-byte aligned");
+  SibFwd<float> t;
+  bool xvec, ovec;
+  SGR_REQUIRE(sib_fwd_table(t, D, xs, weights, biases, outs, x_strides, H, W, xvec, ovec), "sgr_gn_resize_siblings_fwd: NULL tensor of a sibling");
+  const GnStrides ss{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]};
+  const int cpg = C / G, HW = H * W;
+  const long long n = (long long)cpg * HW;
+  const int S = gn_slices(n);
+  const long long stride = 2ll * B * G * S;
+  const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws;
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 mgrid(S, G * D, B), mblock(n <= 2048 ? 64 : kGThreads);
+  if (xvec)
+    hipLaunchKernelGGL((gn_sib_moments_kernel<true, float>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
+  else
+    hipLaunchKernelGGL((gn_sib_moments_kernel<false, float>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
+  const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 1) / 2)), C * D + Cs, B), block(kGThreads);
+  const bool vec = Ws % 2 == 0 && ovec;
+#define SIB_RS_ARGS t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, Hs, Ws, sch, scw, S, eps
+  if (W == Ws) {
+    if (vec) hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<true, true>), grid, block, 0, st, SIB_RS_ARGS);
+    else hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<false, true>), grid, block, 0, st, SIB_RS_ARGS);
+  } else {
+    if (vec) hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<true, false>), grid, block, 0, st, SIB_RS_ARGS);
+    else hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<false, false>), grid, block, 0, st, SIB_RS_ARGS);
+  }
+#undef SIB_RS_ARGS
+  return sgr_check((int)hipGetLastError(), "sgr_gn_resize_siblings_fwd");
+}
+
+extern "C" int sgr_gn_resize_siblings_bwd(int D, const float* const* gs, const float* const* xs, const float* const* weights, const float* const* biases,
+                                          const float* stats, float* const* dxs, float* const* dweights, float* const* dbiases, float* dskip, float* workspace,
+                                          int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides, void* stream) {
+  SGR_REQUIRE(gs, "sgr_gn_resize_siblings_bwd: NULL cotangent");
+  SIB_CHECK_SIZES("sgr_gn_resize_siblings_bwd");
+  SGR_REQUIRE(Hs > 0 && Ws > 0, "sgr_gn_resize_siblings_bwd: non-positive size");
+  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), "sgr_gn_resize_siblings_bwd: outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");
+  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), "sgr_gn_resize_siblings_bwd: Hs * Ws out of range");
+  SibBwd<float> t;
+  bool side, anyg, anyw, anydx;
+  SGR_REQUIRE(sib_bwd_table(t, D, gs, xs, weights, biases, dxs, dweights, dbiases, x_strides, side, anyg, anyw, anydx), "sgr_gn_resize_siblings_bwd: NULL tensor");
+  SGR_REQUIRE(anyg, "sgr_gn_resize_siblings_bwd: NULL cotangent");
+  SGR_REQUIRE(side || dskip, "sgr_gn_resize_siblings_bwd: no gradient requested");
+  SGR_REQUIRE(!side || (stats && workspace), "sgr_gn_resize_siblings_bwd: NULL tensor");
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_siblings_bwd: the workspace must be 8-byte aligned");
+  SGR_SUPPORTED(sib_bwd_strides_fit(t, D, H, W), "sgr_gn_resize_siblings_bwd: negative or out-of-range plane strides");
+  const int cpg = C / G, HW = H * W, P = rs_bwd_slices(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  SibWs ws;
+  ws.base = workspace;
+  ws.coef = 4ll * B * C * P;
+  ws.dy = ws.coef + g_coef_floats(B, G);
+  ws.da = ws.dy + (long long)B * C * HW;
+  ws.stride = sib_block(ws.da + (long long)B * C * Hs * Ws);
+  {      // step 1: the upsample's adjoint of the channels somebody wants
+    const int y_begin = side ? 0 : C * D, y_end = dskip ? C * D + Cs : C * D;
+    const dim3 grid(g_bwd_slices(Hs, Ws), y_end - y_begin, B);
+    if (Ws % 2 == 0 && sib_g_vec(t, D))
+      hipLaunchKernelGGL(gn_sib_up_adjoint_kernel<true>, grid, dim3(kGThreads), 0, st, t, D, ws, dskip, C, Cs, Hs, Ws, y_begin);
+    else
+      hipLaunchKernelGGL(gn_sib_up_adjoint_kernel<false>, grid, dim3(kGThreads), 0, st, t, D, ws, dskip, C, Cs, Hs, Ws, y_begin);
+  }
+  if (side) {
+    const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws, inh = (float)Hs / (float)H, inw = (float)Ws / (float)W;
+    const dim3 grid1(P, C * D, B);
+    if (W == Ws)
+      hipLaunchKernelGGL(gn_sib_rs_bwd_pass1_kernel<1>, grid1, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
+    else
+      hipLaunchKernelGGL(gn_sib_rs_bwd_pass1_kernel<kRsFan>, grid1, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
+    hipLaunchKernelGGL(gn_sib_bwd_fold_kernel, dim3(B * G + (anyw ? C : 0), D), dim3(64), 0, st, t, ws, B, C, cpg, P, (double)cpg * HW);
+    if (anydx) {
+      const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C * D, B);
+      if (sib_dx_vec(t, D, H, W) && aligned16({workspace}))
+        hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<true, float>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
+      else
+        hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<false, float>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
+    }
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_gn_resize_siblings_bwd");
 }

@@ -1,17 +1,20 @@
 // torch.autocast rules for torch.ops.sgrender.* (DESIGN.md section 8j): what an operator does with its floating tensors when it is called
 // inside `with torch.autocast('cuda', dtype=...)`.  With autocast off the Autocast key is not in the dispatch set and nothing here runs.
 //
-//   fp32 policy   every functional operator but gn_stage / gn_stage_bwd: floating tensors (optional ones and lists included) are cast to
+//   fp32 policy   every functional operator but gn_stage / gn_stage_bwd and their sibling forms: floating tensors (optional ones and lists included) are cast to
 //                 fp32 and the result is fp32 -- what PyTorch does for its own group_norm, losses and interpolate.  The render layer, the
 //                 objectives, the solver, the heads and the exact-fp32 MFMA convolutions have fp32 kernels only.
 //   gn_stage      a bf16 x stays bf16 and skip is cast to it (native bf16 kernels, sgr_gn_stage.hip); anything else -- an fp16 x under an
 //                 fp16 autocast too -- is cast to fp32 with its skip.  weight and bias are cast to fp32 either way.
 //   gn_stage_bwd  the same rule on (cotangent, x): bf16 stays when x (or, without x, the cotangent) is bf16.
+//   gn_stage_siblings / _bwd   gn_stage's rule on the lists: bf16 stays when every x (without any x: every cotangent) is bf16.
 //   fall through  operators that write into an argument (rescale_grads_, rescale_grads6_, allreduce_sum_, light_objective_stage2(_brdf):
 //                 a cast copy would take the write) and those without a tensor argument: no kernel here, PyTorch's fall-through applies.
 //
 // Written with at::autocast::cached_cast under an ExcludeDispatchKeyGuard, as PyTorch's own rules are: the casts are ordinary differentiable
 // `to` calls, so the gradients come back in the callers' dtypes.
+#include <algorithm>
+
 #include <ATen/autocast_mode.h>
 
 #include "sgr_torch_common.hpp"
@@ -34,7 +37,8 @@ void autocast_fp32(const c10::OperatorHandle& op, torch::jit::Stack* stack) {
     if (v.isTensor()) {      // Tensor and a Tensor? that is given
       v = cached_cast(at::kFloat, v.toTensor(), kDev);
     } else if (v.isTensorList()) {
-      v = cached_cast(at::kFloat, v.toTensorVector(), kDev);
+      const std::vector<Tensor> ts = v.toTensorVector();
+      v = cached_cast(at::kFloat, at::TensorList(ts), kDev);      // as a TensorList: a std::vector would pick cached_cast's pass-through template
     }
   }
   op.callBoxed(stack);
@@ -61,6 +65,40 @@ T4 gn_stage_bwd_autocast(const Tensor& g, const OT& x, const OT& weight, const O
                  cached_cast(at::kFloat, stats, kDev), C, Cs, G, nX, nW, nB, nS);
 }
 
+// the sibling forms of gn_stage (sgr_torch_gn_siblings.cpp): gn_stage's rule on lists -- bf16 stays when every x is bf16
+using TL = at::TensorList;
+using TV = std::vector<Tensor>;
+using SibFwdSig = std::tuple<TV, Tensor>(TL, TL, TL, const Tensor&, int64_t, double);
+using SibBwdSig = std::tuple<TV, TV, TV, Tensor>(TL, TL, TL, TL, const OT&, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, bool);
+
+// the I/O type of a list: bf16 when it has a non-empty tensor and all of those are bf16
+bool all_bf16(TL ts) {
+  bool any = false;
+  for (const Tensor& t : ts)
+    if (t.defined() && t.numel()) {
+      if (t.scalar_type() != at::kBFloat16) return false;
+      any = true;
+    }
+  return any;
+}
+
+std::tuple<TV, Tensor> gn_stage_siblings_autocast(TL xs, TL weights, TL biases, const Tensor& skip, int64_t G, double eps) {
+  c10::impl::ExcludeDispatchKeyGuard no_autocast(autocast_keys());
+  const at::ScalarType io = all_bf16(xs) ? at::kBFloat16 : at::kFloat;
+  static auto op = find_op<SibFwdSig>("sgrender::gn_stage_siblings");
+  return op.call(cached_cast(io, xs, kDev), cached_cast(at::kFloat, weights, kDev), cached_cast(at::kFloat, biases, kDev), cached_cast(io, skip, kDev), G, eps);
+}
+
+std::tuple<TV, TV, TV, Tensor> gn_stage_siblings_bwd_autocast(TL gs, TL xs, TL weights, TL biases, const OT& stats, int64_t C, int64_t Cs, int64_t G, int64_t H, int64_t W,
+                                                              int64_t nX, int64_t nW, int64_t nB, bool nS) {
+  c10::impl::ExcludeDispatchKeyGuard no_autocast(autocast_keys());
+  const bool any_x = std::any_of(xs.begin(), xs.end(), [](const Tensor& t) { return t.defined() && t.numel() > 0; });
+  const at::ScalarType io = all_bf16(any_x ? xs : gs) ? at::kBFloat16 : at::kFloat;
+  static auto op = find_op<SibBwdSig>("sgrender::gn_stage_siblings_bwd");
+  return op.call(cached_cast(io, gs, kDev), cached_cast(io, xs, kDev), cached_cast(at::kFloat, weights, kDev), cached_cast(at::kFloat, biases, kDev),
+                 cached_cast(at::kFloat, stats, kDev), C, Cs, G, H, W, nX, nW, nB, nS);
+}
+
 // every functional operator with a tensor argument, file by file as they are defined
 constexpr const char* kFp32Ops[] = {
     // sgr_torch.cpp
@@ -72,8 +110,8 @@ constexpr const char* kFp32Ops[] = {
     "brdf_objective_fwd", "brdf_objective_finalize", "brdf_objective_bwd", "brdf_objective", "batch_ranking_loss_fwd", "batch_ranking_loss_bwd", "batch_ranking_loss",
     // sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_bilateral.cpp
     "brdf_encoder_input", "brdf_heads", "brdf_heads_bwd", "bilateral_grid", "bilateral_solve_fwd", "bilateral_solve_bwd", "bilateral_solve",
-    // sgr_torch_gn_resize.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp
-    "gn_resize", "gn_resize_bwd", "final_conv", "final_conv_bwd", "light_final_conv", "light_final_conv_bwd", "encoder_conv", "encoder_conv_bwd",
+    // sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp (the resize form), sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp
+    "gn_resize", "gn_resize_bwd", "gn_resize_siblings", "gn_resize_siblings_bwd", "final_conv", "final_conv_bwd", "light_final_conv", "light_final_conv_bwd", "encoder_conv", "encoder_conv_bwd",
 };
 
 }  // namespace
@@ -82,4 +120,6 @@ TORCH_LIBRARY_IMPL(sgrender, Autocast, m) {
   for (const char* name : kFp32Ops) m.impl(name, torch::CppFunction::makeFromBoxedFunction<&autocast_fp32>());
   m.impl("gn_stage", &gn_stage_autocast);
   m.impl("gn_stage_bwd", &gn_stage_bwd_autocast);
+  m.impl("gn_stage_siblings", &gn_stage_siblings_autocast);
+  m.impl("gn_stage_siblings_bwd", &gn_stage_siblings_bwd_autocast);
 }

@@ -1,4 +1,4 @@
-// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
+// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
 // resolved ONCE for the whole extension, and the few helpers every operator file needs around it.
 //
 // The C ABI stays the drop-in boundary: resolved with dlopen at first use ($SGR_LIB, else the libsgrender.so next to the extension's
@@ -54,6 +54,9 @@ using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Te
   X(sgr_brdf_input_workspace_floats) X(sgr_brdf_input_fwd) X(sgr_brdf_heads_fwd) X(sgr_brdf_heads_bwd)                          \
   X(sgr_gn_stage_workspace_floats) X(sgr_gn_stage_fwd) X(sgr_gn_stage_bwd) X(sgr_gn_stage_fwd_bf16) X(sgr_gn_stage_bwd_bf16)        \
   X(sgr_gn_resize_workspace_floats) X(sgr_gn_resize_fwd) X(sgr_gn_resize_bwd)                                                       \
+  X(sgr_gn_stage_siblings_workspace_floats) X(sgr_gn_stage_siblings_fwd) X(sgr_gn_stage_siblings_bwd)                               \
+  X(sgr_gn_stage_siblings_fwd_bf16) X(sgr_gn_stage_siblings_bwd_bf16)                                                               \
+  X(sgr_gn_resize_siblings_workspace_floats) X(sgr_gn_resize_siblings_fwd) X(sgr_gn_resize_siblings_bwd)                            \
   X(sgr_gn_moments) X(sgr_final_conv_workspace_floats) X(sgr_final_conv_fwd) X(sgr_final_conv_bwd)                              \
   X(sgr_light_final_conv_workspace_floats) X(sgr_light_final_conv_fwd) X(sgr_light_final_conv_bwd)                        \
   X(sgr_encoder_conv_workspace_floats) X(sgr_encoder_conv_fwd) X(sgr_encoder_conv_bwd)

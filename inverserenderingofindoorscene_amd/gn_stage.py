@@ -10,6 +10,9 @@
   ``group_norm_relu_resize(x, weight, bias, num_groups, size, eps)``  ``F.interpolate(F.relu(dgn6(x)), size, mode='bilinear')``: the final
                                                                       stage's resize to the image (models.py:183-186, 330-333)
   ``GroupNormReLU(num_groups, num_channels, eps, resize=False)``      the module form; ``weight`` / ``bias`` load a checkpoint's ``gnK.*``
+  ``group_norm_relu_upcat_siblings(xs, weights, biases, num_groups, skip, eps)``   the upcat stage of ``D`` sibling decoders on one ``skip``
+  ``group_norm_relu_resize_upcat_siblings(...)``                      in one call (the reference runs four ``decoder0`` and three
+  ``SiblingGroupNormReLU(stages, resize=False)``                      ``decoderLight`` instances on the same encoder features)
 
 Eager PyTorch spends four launches forward on a decoder stage (GroupNorm, ReLU, ``cat``, ``upsample_bilinear2d``) and keeps three maps for
 the backward; here it is two launches forward and three backward, and ``x`` with the per-group statistics is all that is kept.  The resize
@@ -18,14 +21,22 @@ forms are two launches forward and four (without a skip: three) backward and kee
 Mixed precision: the two same-size forms also take ``x`` and ``skip`` in ``torch.bfloat16`` (together; ``weight`` and
 ``bias`` stay fp32) and return bf16 -- the fp32 result on the upcast input, rounded once, bit for bit, with ``dx`` / ``dskip`` in bf16 and
 ``dweight`` / ``dbias`` in fp32; the node keeps the bf16 ``x``.  Under ``torch.autocast('cuda', dtype=torch.bfloat16)`` a bf16 ``x`` stays bf16
-and ``skip`` and the parameters are cast as needed; the resize forms proper run in fp32 there.  fp16 is refused as before."""
+and ``skip`` and the parameters are cast as needed; the resize forms proper run in fp32 there.  fp16 is refused as before.
+
+Siblings: at stage ``k`` the four BRDF decoders (three light decoders) do the same thing on the same shapes with the
+same skip; only ``x`` and the ``dgnK`` parameters differ.  The sibling forms run that stage for all of them with the launches of one
+(two forward, three -- resize: four -- backward), read a skip channel once, and return ONE ``dskip``, the cotangents' contributions added
+in sibling order in fp32.  Every other result is the single form's, bit for bit."""
 from __future__ import annotations
 
 import torch
 
 from . import ops as _ops      # noqa: F401  (loads libsgrender_torch.so)
 
-__all__ = ["group_norm_relu", "group_norm_relu_upcat", "group_norm_relu_resize", "group_norm_relu_resize_upcat", "GroupNormReLU"]
+__all__ = ["group_norm_relu", "group_norm_relu_upcat", "group_norm_relu_resize", "group_norm_relu_resize_upcat", "GroupNormReLU",
+           "group_norm_relu_upcat_siblings", "group_norm_relu_resize_upcat_siblings", "SiblingGroupNormReLU"]
+
+MAX_SIBLINGS = 8
 
 _sg = torch.ops.sgrender
 
@@ -102,3 +113,80 @@ class GroupNormReLU(torch.nn.Module):
 
     def extra_repr(self):
         return f"{self.num_groups}, {self.num_channels}, eps={self.eps}" + (", resize=True" if self.resize else "")
+
+
+def _check_siblings(who, xs, weights, biases, num_groups, skip):
+    """the refusals of the sibling forms, before any launch (the operators repeat them for callers of ``torch.ops``)"""
+    xs, weights, biases = list(xs), list(weights), list(biases)
+    if not 1 <= len(xs) <= MAX_SIBLINGS:
+        raise RuntimeError(f"sgrender: {who}: the number of siblings must be 1 .. {MAX_SIBLINGS}, got {len(xs)}")
+    if len(weights) != len(xs) or len(biases) != len(xs):
+        raise RuntimeError(f"sgrender: {who}: {len(xs)} xs but {len(weights)} weights and {len(biases)} biases")
+    if skip is None:
+        raise RuntimeError(f"sgrender: {who}: skip is None; the sibling forms share one skip (group_norm_relu is the form without a skip)")
+    for d, x in enumerate(xs):
+        if tuple(x.shape) != tuple(xs[0].shape):
+            raise RuntimeError(f"sgrender: {who}: the siblings must have one shape, got xs[0] {tuple(xs[0].shape)} and xs[{d}] {tuple(x.shape)}")
+        if x.dtype != xs[0].dtype:
+            raise RuntimeError(f"sgrender: {who}: the siblings must have one dtype, got xs[0] {xs[0].dtype} and xs[{d}] {x.dtype}")
+        if x.device != xs[0].device:
+            raise RuntimeError(f"sgrender: {who}: tensors on different devices (xs[0] {xs[0].device}, xs[{d}] {x.device})")
+    if xs[0].dim() == 4 and (int(num_groups) <= 0 or xs[0].shape[1] % int(num_groups) != 0):
+        raise RuntimeError(f"sgrender: {who}: the channel count {xs[0].shape[1]} is not a multiple of num_groups {num_groups}")
+    return xs, weights, biases
+
+
+def group_norm_relu_upcat_siblings(xs, weights, biases, num_groups: int, skip, eps: float = 1e-5):
+    """:func:`group_norm_relu_upcat` for ``D`` sibling decoders at once: a tuple of ``D`` tensors ``[B, C + Cs, 2H, 2W]`` from ``xs[d] [B,C,H,W]``
+    (one shape, dtype and device; fp32, or bf16 with a bf16 ``skip``), fp32 ``weights[d]`` / ``biases[d] [C]`` and ONE ``skip [B,Cs,H,W]``,
+    ``1 <= D <= 8``.  ``outs[d]`` is ``group_norm_relu_upcat(xs[d], weights[d], biases[d], num_groups, skip, eps)`` bit for bit, and so are the
+    gradients of ``xs[d]``, ``weights[d]`` and ``biases[d]``; the gradient of ``skip`` is ``((s_0 + s_1) + s_2) + ...`` in fp32, ``s_d`` the
+    single form's contribution for the cotangent of ``outs[d]`` -- what autograd's ``D - 1`` adds would give in that order, without the
+    ``D`` maps.  A result left out of the loss is left out of the sum.  One autograd node keeps the ``xs``, the parameters and the
+    ``[D,B,G,4]`` statistics; ``skip`` is not kept."""
+    xs, weights, biases = _check_siblings("group_norm_relu_upcat_siblings", xs, weights, biases, num_groups, skip)
+    return tuple(_sg.gn_stage_siblings(xs, weights, biases, skip, int(num_groups), float(eps))[0])
+
+
+def group_norm_relu_resize_upcat_siblings(xs, weights, biases, num_groups: int, skip, eps: float = 1e-5):
+    """:func:`group_norm_relu_resize_upcat` for ``D`` siblings: ``skip [B,Cs,Hs,Ws]`` with ``H <= Hs <= 2H`` and ``W <= Ws <= 2W`` per axis (fp32
+    only); anything else raises.  With ``(Hs, Ws) == (H, W)`` it is :func:`group_norm_relu_upcat_siblings`, bit for bit."""
+    who = "group_norm_relu_resize_upcat_siblings"
+    xs, weights, biases = _check_siblings(who, xs, weights, biases, num_groups, skip)
+    if skip.dim() == 4 and xs[0].dim() == 4:
+        (h, w), (hs, ws) = xs[0].shape[2:], skip.shape[2:]
+        if (hs, ws) == (h, w):
+            return tuple(_sg.gn_stage_siblings(xs, weights, biases, skip, int(num_groups), float(eps))[0])
+        if not (h <= hs <= 2 * h and w <= ws <= 2 * w):
+            raise RuntimeError(f"sgrender: {who}: the skip {hs}x{ws} is outside the resize domain of x {h}x{w} (H <= Hs <= 2H and W <= Ws <= 2W per axis); "
+                               "any other size stays the caller's composition")
+    return tuple(_sg.gn_resize_siblings(xs, weights, biases, skip, int(num_groups), float(eps))[0])
+
+
+class SiblingGroupNormReLU(torch.nn.Module):
+    """``D`` :class:`GroupNormReLU` modules -- the ``dgnK`` of ``D`` sibling decoders -- behind one fused call.  ``stages`` are kept as an
+    ``nn.ModuleList`` and their parameters are used as they are: ``stages[d]`` may stay a member of its decoder too, and a reference
+    checkpoint's ``dgnK.*`` keys load per sibling exactly as before (here under ``stages.<d>.``).  ``forward(xs, skip)`` returns the tuple of
+    :func:`group_norm_relu_upcat_siblings`; with ``resize=True`` a ``skip`` of another size is accepted
+    (:func:`group_norm_relu_resize_upcat_siblings`)."""
+
+    def __init__(self, stages, resize: bool = False):
+        super().__init__()
+        stages = list(stages)
+        if not 1 <= len(stages) <= MAX_SIBLINGS:
+            raise ValueError(f"sgrender: SiblingGroupNormReLU: the number of siblings must be 1 .. {MAX_SIBLINGS}, got {len(stages)}")
+        for m in stages:
+            if not isinstance(m, GroupNormReLU):
+                raise TypeError(f"sgrender: SiblingGroupNormReLU: stages must be GroupNormReLU modules, got {type(m).__name__}")
+            if (m.num_groups, m.num_channels, m.eps) != (stages[0].num_groups, stages[0].num_channels, stages[0].eps):
+                raise ValueError("sgrender: SiblingGroupNormReLU: the siblings must share num_groups, num_channels and eps")
+        self.stages = torch.nn.ModuleList(stages)
+        self.resize = bool(resize)
+
+    def forward(self, xs, skip):
+        s0 = self.stages[0]
+        f = group_norm_relu_resize_upcat_siblings if self.resize else group_norm_relu_upcat_siblings
+        return f(xs, [m.weight for m in self.stages], [m.bias for m in self.stages], s0.num_groups, skip, s0.eps)
+
+    def extra_repr(self):
+        return f"siblings={len(self.stages)}" + (", resize=True" if self.resize else "")

@@ -17,7 +17,7 @@ wrappers cost ~0.15 ms per step); the C++ extension is the one implementation of
   (backward)  sg_to_env_bwd, render_env_bwd_env, render_bwd_brdf, fused_render_bwd_sg, render_loss_bwd, recon_loss_bwd, light_heads_bwd
 
 Inside ``torch.autocast('cuda', ...)`` every functional operator has a rule (``csrc/sgr_torch_autocast.cpp``): floating
-inputs are cast to fp32 and the result is fp32, except ``sgrender::gn_stage`` / ``gn_stage_bwd``, which keep a bf16 ``x``.  Operators that write
+inputs are cast to fp32 and the result is fp32, except ``sgrender::gn_stage`` / ``gn_stage_bwd`` and their sibling forms, which keep a bf16 ``x``.  Operators that write
 into an argument (``rescale_grads_``, ``allreduce_sum_`` ...) fall through.  With autocast off nothing is cast.
 
 There is no CPU implementation: CPU tensors raise, a missing library raises ``SgrenderUnavailable``.

@@ -6,6 +6,9 @@ at batch 16, forward and forward + backward.
     rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --profile     # the fused calls only, few repetitions
     python tools/gn_stage_bench.py --dtype bf16 [--out FILE.json]                        # mixed precision, see below
     rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --dtype bf16 --profile
+    python tools/gn_stage_bench.py --siblings 4 --only dec_ [--out FILE.json]            # sibling decoders, see below
+    python tools/gn_stage_bench.py --siblings 3 --only light_
+    rocprofv3 --kernel-trace --stats ... -- python tools/gn_stage_bench.py --siblings 4 --only dec_ --profile
 
 At 240x320 ``decoder0``'s second stage works at 14x20 against a 15x20 skip: the reference's resize branch.  ``dec_dgn2_plain`` times the plain
 form there (GroupNorm + ReLU alone, as before the resize was fused); ``dec_dgn2``, ``light_dgn2``, ``light_dgn3`` and ``dec_final`` are the real
@@ -22,7 +25,13 @@ operator; the fp32 operator on the same values; the eager composition under ``to
 same bf16 ``x`` and ``skip`` (autocast runs ``group_norm`` in fp32: it upcasts first).  The algorithmic bytes of the bf16 operator are half
 the fp32 stage's, as every tensor it reads and writes is; the masked adjoint that the upsampling backward writes and re-reads stays fp32, so
 that form's true floor is a little higher and the printed share understates it.  Every ratio is printed against both other candidates; where the bf16 operator is slower or the spreads overlap the line says
-so in capitals."""
+so in capitals.
+
+``--siblings D`` takes the upcat stages of the list (``--only PREFIX`` selects ``dec_`` for ``decoder0``'s four siblings or
+``light_`` for ``decoderLight``'s three) and alternates two candidates in one process: ONE call of the sibling form, and ``D`` calls of the
+single form on the same tensors, whose backward is one ``torch.autograd.grad`` over the ``D`` results -- autograd then adds the ``D`` maps of
+``dskip`` with ``D - 1`` eager adds, which is what a cascade step did before the sibling forms.  Algorithmic bytes of a row: the ``D`` inputs
+once, the skip once, the ``D`` results once; for the backward the ``D`` cotangents, the ``D`` inputs twice, ``D`` ``dx`` and one ``dskip``."""
 import argparse
 import json
 import os
@@ -159,6 +168,65 @@ def main_bf16(args, sgr):
             json.dump(rec, f, indent=1)
 
 
+def main_siblings(args, sgr):
+    """the upcat stages for D sibling decoders: one sibling call against D single calls (and autograd's D - 1 adds of dskip)"""
+    D = args.siblings
+    reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
+    rec = {"device": torch.cuda.get_device_name(0), "reps": reps, "batch": B, "siblings": D, "ms": {}, "bytes": {}}
+    for name, C, G, H, W, Cs, *rest in STAGES:
+        if not Cs or not name.startswith(args.only) or name.endswith("_plain"):
+            continue
+        Hs, Ws = rest[0] if rest else (H, W)
+        g = torch.Generator().manual_seed(len(name) + C)
+        xs = [torch.randn(B, C, H, W, generator=g).cuda().requires_grad_(True) for _ in range(D)]
+        ws = [torch.randn(C, generator=g).cuda().requires_grad_(True) for _ in range(D)]
+        bs = [(0.3 * torch.randn(C, generator=g)).cuda().requires_grad_(True) for _ in range(D)]
+        skip = torch.randn(B, Cs, Hs, Ws, generator=g).cuda().requires_grad_(True)
+        cts = [torch.randn(B, C + Cs, 2 * Hs, 2 * Ws, generator=g).cuda() for _ in range(D)]
+        leaves = xs + ws + bs + [skip]
+        one = sgr.group_norm_relu_resize_upcat if rest else sgr.group_norm_relu_upcat
+        many = sgr.group_norm_relu_resize_upcat_siblings if rest else sgr.group_norm_relu_upcat_siblings
+        cands = dict(siblings=lambda: list(many(xs, ws, bs, G, skip)), singles=lambda: [one(x, w, b, G, skip) for x, w, b in zip(xs, ws, bs)])
+        fns = {}
+        for k, f in cands.items():
+            if args.profile and k != "siblings":
+                continue
+
+            def fwd(f=f):
+                with torch.no_grad():
+                    return f()
+            fns[f"{k}_fwd"] = fwd
+            fns[f"{k}_fwd_bwd"] = lambda f=f: torch.autograd.grad(f(), leaves, grad_outputs=cts)
+        t = timed(fns, reps, warm)
+        m, ms = B * H * W * 4, B * Hs * Ws * 4
+        b_fwd = D * C * m + Cs * ms + D * 4 * (C + Cs) * ms
+        b_bwd = D * 4 * (C + Cs) * ms + 2 * D * C * m + D * C * m + Cs * ms
+        rec["bytes"][name] = dict(forward=b_fwd, backward=b_bwd)
+        for k, v in t.items():
+            med = statistics.median(v)
+            rec["ms"][f"{name}_{k}"] = dict(median=med, min=v[0], max=v[-1])
+            nb = b_fwd if k.endswith("_fwd") else b_fwd + b_bwd
+            floor = nb / (HBM_TBPS * 1e12) * 1e6
+            note = f"algorithmic {nb / 1e6:.1f} MB: floor {floor:.1f} us at {HBM_TBPS} TB/s (share {floor / (med * 1e3):.2f})"
+            print(f"{name + '_' + k:32s} median {med * 1e3:9.1f} us  min {v[0] * 1e3:9.1f}  max {v[-1] * 1e3:9.1f}  {note}")
+        if not args.profile:
+            for k in ("fwd", "fwd_bwd"):
+                sib, sin = rec["ms"][f"{name}_siblings_{k}"], rec["ms"][f"{name}_singles_{k}"]
+                s = sin["median"] / sib["median"]
+                rec["ms"][f"{name}_singles_over_siblings_{k}"] = s
+                if s >= 1:
+                    verdict = "the difference exceeds the spread" if sin["min"] > sib["max"] else "THE SPREADS OVERLAP"
+                else:
+                    verdict = "THE SIBLING CALL IS SLOWER" + ("" if sib["min"] > sin["max"] else ", the spreads overlap")
+                print(f"{name + '_' + k:32s} D = {D}: singles / siblings = {s:.2f}x  ({verdict})")
+        del xs, ws, bs, skip, cts, leaves, cands, fns
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=80)
@@ -166,10 +234,14 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--out", default="")
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--siblings", type=int, default=0, help="D sibling decoders: the sibling call against D single calls")
+    ap.add_argument("--only", default="", help="with --siblings: the stages whose name starts with this (dec_, light_)")
     args = ap.parse_args()
     import inverserenderingofindoorscene_amd as sgr
     if not torch.cuda.is_available():
         raise SystemExit("gn_stage_bench needs a GPU")
+    if args.siblings:
+        return main_siblings(args, sgr)
     if args.dtype == "bf16":
         return main_bf16(args, sgr)
     reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
