@@ -71,7 +71,13 @@ class BilateralLayer(nn.Module):
         return _unit_scale(image), _unit_scale(feature)
 
     def confidence(self, image, feature, pred):
-        """The confidence CNN alone (BilateralLayer.py:235-266): plain PyTorch, runs on any device."""
+        """The confidence CNN alone (BilateralLayer.py:235-266): plain PyTorch, runs on any device.  Inside an autocast region it runs in
+        fp32 like the solver it feeds: the inputs are cast to fp32 and its convolutions are kept out of autocast."""
+        image, feature, pred = _ops.autocast_fp32(image, feature, pred)
+        with _ops.autocast_off(image, pred):
+            return self._confidence(image, feature, pred)
+
+    def _confidence(self, image, feature, pred):
         image, _ = self._scaled(image, feature)
         x = torch.cat([image, pred], dim=1).detach()
         x1 = F.relu(self.gn1(self.conv1(self.pad1(x))), True)
@@ -86,6 +92,7 @@ class BilateralLayer(nn.Module):
     def forward(self, image, feature, pred):
         """-> (refined pred, confidence).  The solver's guide is the scaled, detached ``feature`` (the albedo prediction at every
         call site of the reference), ``image`` only feeds the confidence CNN (BilateralLayer.py:268)."""
+        image, feature, pred = _ops.autocast_fp32(image, feature, pred)
         conf = self.confidence(image, feature, pred)
         _, guide = self._scaled(image, feature)
         out = bilateral_solve(guide.detach(), pred, conf, **self.grid_params, **self.bs_params)

@@ -66,6 +66,22 @@ c10::Device require_hip(std::initializer_list<const Tensor*> ts) {
   TORCH_CHECK(have, "sgrender: no tensor argument");
   return dev;
 }
+// require_hip's dtype refusal alone, for Meta kernels: a fake-tensor run must not pass where the device kernel raises
+void require_fp32(std::initializer_list<const Tensor*> ts) {
+  for (const Tensor* t : ts)
+    if (t && t->defined()) TORCH_CHECK(t->scalar_type() == at::kFloat, "sgrender: fp32 tensors required, got ", t->scalar_type());
+}
+// a Meta kernel behind that refusal, applied to every tensor argument (optional ones when given): `&fp32_only<&f_meta>::call`
+inline void require_fp32_arg(const Tensor& t) { require_fp32({&t}); }
+inline void require_fp32_arg(const OptTensor& t) { if (t.has_value()) require_fp32({&*t}); }
+template <class T> void require_fp32_arg(const T&) {}
+template <auto F> struct fp32_only;
+template <class R, class... A, R (*F)(A...)> struct fp32_only<F> {
+  static R call(A... a) {
+    (require_fp32_arg(a), ...);
+    return F(std::forward<A>(a)...);
+  }
+};
 const Tensor* opt(const OptTensor& t) { return t.has_value() && t->defined() ? &*t : nullptr; }
 
 
@@ -1229,6 +1245,7 @@ T8 objective_stage2(STAGE2_ARGS, bool need_grad, MapWants want) {
   return {render_err, g_axis, g_lamb, g_weight, want.albedo ? g_alb : Tensor(), want.normal ? g_nrm : Tensor(), want.rough ? g_rgh : Tensor(), parts_b};
 }
 T8 objective_stage2_shapes(STAGE2_ARGS, bool need_grad, MapWants want) {
+  require_fp32({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws});
   const auto d = check_sg(axis, lamb, weight);
   check_brdf(albedo, normal, rough);
   check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
@@ -1476,35 +1493,37 @@ TORCH_LIBRARY_IMPL(sgrender, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(sgrender, Meta, m) {
-  m.impl("sg_to_env", &sg_to_env_meta);
-  m.impl("sg_to_env_bwd", &sg_to_env_bwd_meta);
-  m.impl("render_env", &render_env_meta);
-  m.impl("render_env_bwd_env", &render_env_bwd_env_meta);
-  m.impl("render_bwd_brdf", &render_bwd_brdf_meta);
-  m.impl("fused_render", &fused_render_meta);
-  m.impl("fused_render_bwd_sg", &fused_render_bwd_sg_meta);
-  m.impl("lsregress_coef", &lsregress_coef_meta);
-  m.impl("lsregress_diffspec_coef", &lsregress_diffspec_coef_meta);
-  m.impl("render_loss", &render_loss_meta);
-  m.impl("render_loss_bwd", &render_loss_bwd_meta);
-  m.impl("render_loss_finalize", &render_loss_finalize_meta);
-  m.impl("recon_loss_parts", &recon_loss_parts_meta);
-  m.impl("recon_loss_bwd", &recon_loss_bwd_meta);
-  m.impl("light_heads", &light_heads_meta);
-  m.impl("light_heads_bwd", &light_heads_bwd_meta);
-  m.impl("sg_shading", &sg_shading_meta);
-  m.impl("light_albedo_scale", &light_albedo_scale_meta);
-  m.impl("light_encoder_input", &light_encoder_input_meta);
+  // fp32_only: the dtype refusal of the device kernels' require_hip, so that a fake-tensor run raises where the device would
+
+  m.impl("sg_to_env", &fp32_only<&sg_to_env_meta>::call);
+  m.impl("sg_to_env_bwd", &fp32_only<&sg_to_env_bwd_meta>::call);
+  m.impl("render_env", &fp32_only<&render_env_meta>::call);
+  m.impl("render_env_bwd_env", &fp32_only<&render_env_bwd_env_meta>::call);
+  m.impl("render_bwd_brdf", &fp32_only<&render_bwd_brdf_meta>::call);
+  m.impl("fused_render", &fp32_only<&fused_render_meta>::call);
+  m.impl("fused_render_bwd_sg", &fp32_only<&fused_render_bwd_sg_meta>::call);
+  m.impl("lsregress_coef", &fp32_only<&lsregress_coef_meta>::call);
+  m.impl("lsregress_diffspec_coef", &fp32_only<&lsregress_diffspec_coef_meta>::call);
+  m.impl("render_loss", &fp32_only<&render_loss_meta>::call);
+  m.impl("render_loss_bwd", &fp32_only<&render_loss_bwd_meta>::call);
+  m.impl("render_loss_finalize", &fp32_only<&render_loss_finalize_meta>::call);
+  m.impl("recon_loss_parts", &fp32_only<&recon_loss_parts_meta>::call);
+  m.impl("recon_loss_bwd", &fp32_only<&recon_loss_bwd_meta>::call);
+  m.impl("light_heads", &fp32_only<&light_heads_meta>::call);
+  m.impl("light_heads_bwd", &fp32_only<&light_heads_bwd_meta>::call);
+  m.impl("sg_shading", &fp32_only<&sg_shading_meta>::call);
+  m.impl("light_albedo_scale", &fp32_only<&light_albedo_scale_meta>::call);
+  m.impl("light_encoder_input", &fp32_only<&light_encoder_input_meta>::call);
   m.impl("rescale_grads_", &rescale_grads_meta);
   m.impl("attach_grads", &attach_grads_backend);
-  m.impl("light_objective_fwdbwd", &light_objective_fwdbwd_meta);
+  m.impl("light_objective_fwdbwd", &fp32_only<&light_objective_fwdbwd_meta>::call);
   m.impl("light_objective", &light_objective_backend);
-  m.impl("light_objective_stage1", &light_objective_stage1_meta);
+  m.impl("light_objective_stage1", &fp32_only<&light_objective_stage1_meta>::call);
   m.impl("light_objective_stage2", &light_objective_stage2_meta);
-  m.impl("light_objective_stage3", &light_objective_stage3_meta);
+  m.impl("light_objective_stage3", &fp32_only<&light_objective_stage3_meta>::call);
   m.impl("rescale_grads6_", &rescale_grads6_meta);
   m.impl("attach_grads6", &attach_grads6_backend);
-  m.impl("light_objective_brdf_fwdbwd", &light_objective_brdf_fwdbwd_meta);
+  m.impl("light_objective_brdf_fwdbwd", &fp32_only<&light_objective_brdf_fwdbwd_meta>::call);
   m.impl("light_objective_brdf", &light_objective_backend);
   m.impl("light_objective_stage2_brdf", &light_objective_stage2_brdf_meta);
   m.impl("allreduce_sum_", &allreduce_sum_meta);

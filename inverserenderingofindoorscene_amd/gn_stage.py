@@ -116,7 +116,8 @@ class GroupNormReLU(torch.nn.Module):
 
 
 def _check_siblings(who, xs, weights, biases, num_groups, skip):
-    """the refusals of the sibling forms, before any launch (the operators repeat them for callers of ``torch.ops``)"""
+    """the refusals of the sibling forms, before any launch (the operators repeat them for callers of ``torch.ops``).  Inside an autocast
+    region siblings of different floating dtypes are let through: the operators' autocast rules cast the lists to one dtype first."""
     xs, weights, biases = list(xs), list(weights), list(biases)
     if not 1 <= len(xs) <= MAX_SIBLINGS:
         raise RuntimeError(f"sgrender: {who}: the number of siblings must be 1 .. {MAX_SIBLINGS}, got {len(xs)}")
@@ -127,7 +128,7 @@ def _check_siblings(who, xs, weights, biases, num_groups, skip):
     for d, x in enumerate(xs):
         if tuple(x.shape) != tuple(xs[0].shape):
             raise RuntimeError(f"sgrender: {who}: the siblings must have one shape, got xs[0] {tuple(xs[0].shape)} and xs[{d}] {tuple(x.shape)}")
-        if x.dtype != xs[0].dtype:
+        if x.dtype != xs[0].dtype and not (torch.is_autocast_enabled("cuda") and x.is_cuda):      # autocast gives the siblings one dtype; the operator checks after it
             raise RuntimeError(f"sgrender: {who}: the siblings must have one dtype, got xs[0] {xs[0].dtype} and xs[{d}] {x.dtype}")
         if x.device != xs[0].device:
             raise RuntimeError(f"sgrender: {who}: tensors on different devices (xs[0] {xs[0].device}, xs[{d}] {x.device})")

@@ -43,10 +43,11 @@ def _prepool(albedo, normal, rough, R: int, C: int):
     """BRDF maps whose size is not 1x or 2x the env grid (testReal.py:320-346 resizes freely) are
     average-pooled to the grid first -- with torch's own adaptive pooling, so that autograd and
     the window arithmetic are exactly those of models.py:465-469; the kernels then run with
-    ratio 1."""
+    ratio 1.  Inside an autocast region the maps are cast to fp32 first, as the kernels' own pooling of the 1x / 2x sizes sees them."""
     h, w = albedo.shape[2], albedo.shape[3]
     if (h, w) == (R, C) or (h, w) == (2 * R, 2 * C):
         return albedo, normal, rough
+    albedo, normal, rough = _ops.autocast_fp32(albedo, normal, rough, contiguous=True)      # one summation order for every layout
     return (F.adaptive_avg_pool2d(albedo, (R, C)), F.adaptive_avg_pool2d(normal, (R, C)),
             F.adaptive_avg_pool2d(rough, (R, C)))
 
@@ -79,6 +80,7 @@ class output2env:
     def output2env(self, axisOrig, lambOrig, weightOrig):
         """models.py:391-404: returns ``(envmaps, axis, lamb_tan, weight_tan)``."""
         self._check_lobes(axisOrig)
+        axisOrig, = _ops.autocast_fp32(axisOrig)      # returned beside fp32 results: cast once here, so that its gradient is summed in fp32
         env, lamb, weight = _sg.sg_to_env(axisOrig, lambOrig, weightOrig, self.envHeight, self.envWidth, True, True)
         return env, axisOrig, lamb, weight
 

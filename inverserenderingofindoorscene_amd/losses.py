@@ -61,6 +61,32 @@ def _lsregress_diffspec_live(diff, spec, imOrig, diffOrig, specOrig):
     return again * d_scaled, again * s_scaled
 
 
+class _LiveRegressionFp32(torch.autograd.Function):
+    """:func:`_lsregress_diffspec_live` for a call inside an autocast region: forward and backward both run with autocast off, so its
+    matrix products stay fp32 wherever ``backward`` is called (autocast would also cast the products of a backward run inside the region).
+    First order only: the inner graph is differentiated once."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        with torch.enable_grad(), torch.autocast("cuda", enabled=False):
+            ctx.inner = [a.detach().requires_grad_(n) for a, n in zip(args, ctx.needs_input_grad)]
+            ctx.outs = _lsregress_diffspec_live(*ctx.inner)
+        return tuple(o.detach() for o in ctx.outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        live = [t for t in ctx.inner if t.requires_grad]
+        with torch.autocast("cuda", enabled=False):
+            grads = list(torch.autograd.grad(ctx.outs, live, gs, allow_unused=True))
+        return tuple(grads.pop(0) if t.requires_grad else None for t in ctx.inner)
+
+
+def _pool(t, R: int, C: int):
+    """torch's adaptive average pooling to the env grid; inside an autocast region in fp32 and from a contiguous map, as the kernels pool
+    the 1x / 2x sizes (torch's pooling of a channels-last map sums in another order)"""
+    return F.adaptive_avg_pool2d(_ops.autocast_fp32(t, contiguous=True)[0], (R, C))
+
+
 def LSregress(pred, gt, origin):
     """``origin * clamp(<pred,gt> / max(<pred,pred>, 1e-5), 1e-3, 1e3)`` per image (models.py:7-21).
 
@@ -82,6 +108,8 @@ def LSregressDiffSpec(diff, spec, imOrig, diffOrig, specOrig):
     if diff.shape != spec.shape or diff.shape != imOrig.shape:
         raise RuntimeError("sgrender: LSregressDiffSpec needs diff, spec and imOrig of one shape")
     if torch.is_grad_enabled() and (diff.requires_grad or spec.requires_grad):
+        if torch.is_autocast_enabled("cuda") and diff.is_cuda:      # its matrix products are torch's: kept in fp32, like the operators
+            return _LiveRegressionFp32.apply(*_ops.autocast_fp32(diff, spec, imOrig, diffOrig, specOrig))
         return _lsregress_diffspec_live(diff, spec, imOrig, diffOrig, specOrig)
     nb = diff.shape[0]
     coef = _sg.lsregress_diffspec_coef(diff.detach(), spec.detach(), imOrig.detach())
@@ -204,8 +232,7 @@ def render_loss(diffuse, spec, im, seg, envRow: int, envCol: int, group=None) ->
     average-pooled with torch first (same window arithmetic as the reference)."""
     h, w = im.shape[2], im.shape[3]
     if (h, w) != (envRow, envCol) and (h, w) != (2 * envRow, 2 * envCol):
-        im = F.adaptive_avg_pool2d(im, (envRow, envCol))
-        seg = F.adaptive_avg_pool2d(seg, (envRow, envCol))
+        im, seg = _pool(im, envRow, envCol), _pool(seg, envRow, envCol)
     if _sharded(group):
         # this shard's [numerator, raw denominator] (three launches), their sum over the ranks (one all-reduce of two floats: RCCL over
         # xGMI), then the loss value and its gradient scale from the GLOBAL totals (one launch; the autograd node sits on this operator:
@@ -236,9 +263,10 @@ def recon_loss(envmapsPredImage, envmapsBatch, segBRDFBatch, envmapsIndBatch, en
 
     With ``return_scaled=True`` also returns ``envmapsPredScaledImage`` (= pred * coef, a torch broadcast
     multiply -- the reference returns it for logging)."""
+    envmapsPredImage, = _ops.autocast_fp32(envmapsPredImage)      # used twice with return_scaled: cast once, its gradient is summed in fp32
     seg_s = segBRDFBatch
     if tuple(seg_s.shape[2:]) != (envRow, envCol):
-        seg_s = F.adaptive_avg_pool2d(segBRDFBatch, (envRow, envCol))
+        seg_s = _pool(segBRDFBatch, envRow, envCol)
     num, den, coef = _recon_parts(envmapsPredImage, envmapsBatch, seg_s, envmapsIndBatch, offset)
     eh, ew = envmapsPredImage.shape[4], envmapsPredImage.shape[5]
     err = combine_loss_parts(num, den, group, divisor=3.0 * eh * ew)
@@ -310,7 +338,7 @@ def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, la
         # other direction grids / more than 12 lobes: same objective from the unfused HIP kernels (env image materialised)
         env, diffuse, spec = impl.forwardSG(albedoPred, normalPred, roughPred, axisPred, lambPred, weightPred, need_env=True)
         render_err, rendered = render_loss(diffuse, spec, imBatch, segBRDFBatch, R, C, group)
-        seg_s = segBRDFBatch if tuple(segBRDFBatch.shape[2:]) == (R, C) else F.adaptive_avg_pool2d(segBRDFBatch, (R, C))
+        seg_s = segBRDFBatch if tuple(segBRDFBatch.shape[2:]) == (R, C) else _pool(segBRDFBatch, R, C)
         num, den, coef = _recon_parts(env, envmapsBatch, seg_s, envmapsIndBatch, offset)
         recon_err = combine_loss_parts(num, den, group, divisor=3.0 * impl.envHeight * impl.envWidth)
         objective = float(renderWeight) * render_err + float(reconWeight) * recon_err
@@ -319,8 +347,7 @@ def light_objective(renderLayer, albedoPred, normalPred, roughPred, axisPred, la
     im, seg = imBatch, segBRDFBatch
     h, w = im.shape[2], im.shape[3]
     if (h, w) != (R, C) and (h, w) != (2 * R, 2 * C):
-        im = F.adaptive_avg_pool2d(im, (R, C))
-        seg = F.adaptive_avg_pool2d(seg, (R, C))
+        im, seg = _pool(im, R, C), _pool(seg, R, C)
     eh, ew, fov, F0, cam = impl.envHeight, impl.envWidth, impl.fov_deg, float(impl.F0), impl._cam
     handoff = _ops.tan_handoff() and not heads
     # What may require grad is settled before any launch or collective, on BOTH routes (the one-rank operator raised, the
@@ -353,6 +380,9 @@ def _light_objective_sharded(a, n, r, axisPred, lambPred, weightPred, im, seg, e
                              handoff, group, live):
     """The fused objective with the batch sharded over ranks: three stage operators with the two collectives between them.
     ``live``: which of the maps ``a, n, r`` want a gradient (all ``False`` on the default route)."""
+    # the stage-2 operators write into `ws` and so have no autocast rule: inside an autocast region the floating inputs are cast to fp32
+    # here, once and differentiably, so that all three stages and attach_grads see the same tensors and the gradients return through the cast
+    a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind = _ops.autocast_fp32(a, n, r, axisPred, lambPred, weightPred, im, seg, env_gt, env_ind)
     need = any(live) or (torch.is_grad_enabled() and (axisPred.requires_grad or lambPred.requires_grad or weightPred.requires_grad))
     with torch.no_grad():
         diffuse, spec, mask, coef, im_s, seg_s, rendered, coef_ds, sums, ws, lam_t, w_t = _sg.light_objective_stage1(

@@ -24,6 +24,7 @@ There is no CPU implementation: CPU tensors raise, a missing library raises ``Sg
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -68,6 +69,27 @@ def tan_handoff() -> bool:
 
 
 _TAN_HANDOFF_DEFAULT = False     # measured at config 2: +45 us of stores in the (write-bound) forward for -12 us in the backward
+
+
+def autocast_fp32(*ts, contiguous: bool = False):
+    """The operators' fp32 autocast policy for the torch calls the wrappers make themselves (pooling, scaling, the writer operators'
+    arguments): inside ``torch.autocast('cuda', ...)`` every device tensor of a lower-precision floating type is cast to fp32 by a
+    differentiable ``.float()``, as ``csrc/sgr_torch_autocast.cpp`` casts an operator's arguments (fp64 is left alone there too).
+    With autocast off, and for ``None``, fp32 and integer tensors, the arguments come back as they are.  ``contiguous``: inside the region
+    the device tensors are also made contiguous (before torch's pooling, whose summation order depends on the layout)."""
+    if not torch.is_autocast_enabled("cuda"):
+        return ts
+    low = lambda t: t is not None and t.is_cuda and t.is_floating_point() and t.dtype not in (torch.float32, torch.float64)
+    ts = tuple(t.float() if low(t) else t for t in ts)
+    return tuple(t.contiguous() if t is not None and t.is_cuda else t for t in ts) if contiguous else ts
+
+
+def autocast_off(*ts):
+    """Context for a wrapper's own torch code that must not be autocast (matrix products, convolutions): disables the cuda autocast
+    when it is on and a tensor of ``ts`` lives on the device; otherwise a null context."""
+    if torch.is_autocast_enabled("cuda") and any(t is not None and t.is_cuda for t in ts):
+        return torch.autocast("cuda", enabled=False)
+    return contextlib.nullcontext()
 
 
 # --------------------------------------------------------------------------- #
