@@ -13,9 +13,13 @@
 //                                                                rounds 2-3 had a Python custom_op AND a Python autograd.Function)
 //   * CPU:       a boxed fallback that raises -- there is no CPU path and no fallback to one.
 //
-// The C ABI stays the drop-in boundary: sgr_torch_common.hpp resolves it once, at first use, for this file and its siblings of the same
-// extension (sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp) and holds the helpers the three share.  The light objective is ONE path:
+// The C ABI stays the drop-in boundary: sgr_torch_common.hpp resolves it once, at first use, for every operator file of the extension
+// and holds the helpers they share.  The light objective is ONE path:
 // objective_fwdbwd / objective_stage2 / PrecomputedGradsFn serve the SG-only operators and their _brdf twins alike (MapWants).
+//
+// Every operator has ONE check_<op>(args..., bool device) and one list of output shapes, shared by the device and the Meta kernels: a
+// traced graph cannot pass tracing and then fail on the device.  The checks read the caller's tensors, so a refused call copies and
+// allocates nothing.  device kernel: check -> DeviceGuard -> outputs -> .contiguous() inputs -> tables -> the C call; Meta: check -> outputs.
 //
 // Reference call each public operator stands for (file:line relative to the reference checkout):
 //   sg_to_env          output2env.output2env / fromSGtoIm            models.py:371-404
@@ -27,18 +31,13 @@
 //   light_objective    renW * renderErr + recW * reconstErr, fused   wrapperBRDFLight.py:167-207, trainLight.py:237
 //   lsregress_*_coef   LSregress / LSregressDiffSpec coefficients    models.py:7-21, 23-84
 //   sg_shading, light_albedo_scale, light_encoder_input             utils.py:156-195, testReal.py:421-432, wrapperBRDFLight.py:138-156
-#include <link.h>
-
 #include <array>
-#include <cstring>
 #include <deque>
 #include <map>
 #include <mutex>
 #include <vector>
 
 #include "sgr_torch_common.hpp"
-
-#include <rccl/rccl.h>      // declarations only: the functions are resolved from the RCCL PyTorch itself has loaded (rccl() below)
 
 namespace {
 
@@ -48,42 +47,22 @@ using Cam = at::ArrayRef<double>;
 // ------------------------------------------------------------------------------------------------------------------
 // argument checks, constant tables
 // ------------------------------------------------------------------------------------------------------------------
-void require_one(const Tensor& t, c10::Device& dev, bool& have) {
-  TORCH_CHECK(t.is_cuda(), kNoCpu);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, "sgrender: fp32 tensors required, got ", t.scalar_type());
-  if (!have) {
-    dev = t.device();
-    have = true;
-  } else {
-    TORCH_CHECK(t.device() == dev, "sgrender: tensors on different devices (", dev, " vs ", t.device(), ")");
+// fp32 tensors of one device, absent ones skipped; on the device also "no CPU path" (a Meta kernel makes every refusal but that one)
+c10::Device require_hip(std::initializer_list<const Tensor*> ts, bool device = true) {
+  const Tensor* first = nullptr;
+  for (const Tensor* t : ts) {
+    if (!t || !t->defined()) continue;
+    if (device) TORCH_CHECK(t->is_cuda(), kNoCpu);
+    TORCH_CHECK(t->scalar_type() == at::kFloat, "sgrender: fp32 tensors required, got ", t->scalar_type());
+    if (!first) first = t;
+    TORCH_CHECK(t->device() == first->device(), "sgrender: tensors on different devices (", first->device(), " vs ", t->device(), ")");
   }
+  TORCH_CHECK(first, "sgrender: no tensor argument");
+  return first->device();
 }
-c10::Device require_hip(std::initializer_list<const Tensor*> ts) {
-  c10::Device dev(c10::kCUDA, 0);
-  bool have = false;
-  for (const Tensor* t : ts)
-    if (t && t->defined()) require_one(*t, dev, have);
-  TORCH_CHECK(have, "sgrender: no tensor argument");
-  return dev;
-}
-// require_hip's dtype refusal alone, for Meta kernels: a fake-tensor run must not pass where the device kernel raises
-void require_fp32(std::initializer_list<const Tensor*> ts) {
-  for (const Tensor* t : ts)
-    if (t && t->defined()) TORCH_CHECK(t->scalar_type() == at::kFloat, "sgrender: fp32 tensors required, got ", t->scalar_type());
-}
-// a Meta kernel behind that refusal, applied to every tensor argument (optional ones when given): `&fp32_only<&f_meta>::call`
-inline void require_fp32_arg(const Tensor& t) { require_fp32({&t}); }
-inline void require_fp32_arg(const OptTensor& t) { if (t.has_value()) require_fp32({&*t}); }
-template <class T> void require_fp32_arg(const T&) {}
-template <auto F> struct fp32_only;
-template <class R, class... A, R (*F)(A...)> struct fp32_only<F> {
-  static R call(A... a) {
-    (require_fp32_arg(a), ...);
-    return F(std::forward<A>(a)...);
-  }
-};
-const Tensor* opt(const OptTensor& t) { return t.has_value() && t->defined() ? &*t : nullptr; }
-
+const Tensor* opt(const OptTensor& t) { return has(t) ? &*t : nullptr; }
+// numel() from the sizes: a fake tensor with symbolic sizes (torch.compile with dynamic shapes) specialises on sizes() but refuses numel()
+int64_t count(const Tensor& t) { return c10::multiply_integers(t.sizes()); }
 
 struct SgDims { int64_t bn, K, R, C; };
 SgDims check_sg(const Tensor& axis, const Tensor& lamb, const Tensor& weight) {
@@ -108,7 +87,20 @@ BrdfDims check_brdf(const Tensor& albedo, const Tensor& normal, const Tensor& ro
   TORCH_CHECK(bn > 0 && h > 0 && w > 0, "sgrender: zero-sized BRDF maps (batch or image of 0) are not supported, got diffusePred ", albedo.sizes());
   return {bn, h, w};
 }
+// what the constant tables need of the direction grid and the camera (dirs_table / view_table below)
+void check_env_grid(int64_t eh, int64_t ew) { TORCH_CHECK(eh > 0 && ew > 0, "sgrender: envHeight / envWidth must be positive"); }
 void check_cam(Cam cam) { TORCH_CHECK(cam.size() == 3, "sgrender: cameraPos must have three components"); }
+void check_tables(int64_t eh, int64_t ew, Cam cam) { check_env_grid(eh, ew); check_cam(cam); }
+
+// output shapes the operators share
+Tensor env_image(int64_t bn, int64_t R, int64_t C, int64_t eh, int64_t ew, const at::TensorOptions& o) { return at::empty({bn, 3, R, C, eh, ew}, o); }
+Tensor rgb(int64_t bn, int64_t R, int64_t C, const at::TensorOptions& o) { return at::empty({bn, 3, R, C}, o); }
+T3 sg_like(const SgDims& d, const at::TensorOptions& o) {      // axis, lamb, weight (or their gradients)
+  return {at::empty({d.bn, d.K, 3, d.R, d.C}, o), at::empty({d.bn, d.K, d.R, d.C}, o), at::empty({d.bn, 3 * d.K, d.R, d.C}, o)};
+}
+T3 brdf_like(const BrdfDims& b, const at::TensorOptions& o) {      // albedo, normal, rough (or their gradients)
+  return {at::empty({b.bn, 3, b.h, b.w}, o), at::empty({b.bn, 3, b.h, b.w}, o), at::empty({b.bn, 1, b.h, b.w}, o)};
+}
 
 // Constant tables (models.py:353-363, 415-452), created lazily on whichever device the inputs live on.  The reference keeps them
 // as bare attributes on the layer object, created on the current device and never moved by .to(); keying by device keeps that
@@ -168,7 +160,7 @@ int64_t table_cache_count(int64_t kind) {
   return n;
 }
 Tensor dirs_table(const c10::Device& dev, int64_t eh, int64_t ew) {
-  TORCH_CHECK(eh > 0 && ew > 0, "sgrender: envHeight / envWidth must be positive");
+  check_env_grid(eh, ew);
   const TableKey key{0, (int)eh, (int)ew, (int)dev.index(), {0.f, 0.f, 0.f, 0.f}};
   return table(key, dev, api().sgr_dirs_floats((int)eh, (int)ew), [&](float* p) { ok(api().sgr_fill_direction_table(p, (int)eh, (int)ew), "sgr_fill_direction_table"); });
 }
@@ -179,21 +171,26 @@ Tensor view_table(const c10::Device& dev, int64_t R, int64_t C, double fov, Cam 
   return table(key, dev, 3 * R * C, [&](float* p) { ok(api().sgr_fill_view_vectors(p, (int)R, (int)C, (float)fov, c3), "sgr_fill_view_vectors"); });
 }
 
-Tensor none_like(const Tensor& t) { return at::empty({0}, t.options()); }      // operators return tensors only: "not asked for" is an empty tensor
-bool present(const Tensor& t) { return t.defined() && t.numel() > 0; }
 std::vector<double> vec(Cam cam) { return std::vector<double>(cam.begin(), cam.end()); }
 
 // ==================================================================================================================
 // SG -> env image
 // ==================================================================================================================
+SgDims check_sg_to_env(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, bool device) {      // sg_shading's check too
+  require_hip({&axis, &lamb, &weight}, device);
+  const auto d = check_sg(axis, lamb, weight);
+  check_env_grid(eh, ew);
+  return d;
+}
+T3 sg_to_env_outputs(const SgDims& d, int64_t eh, int64_t ew, bool tan, const at::TensorOptions& o) {
+  return {env_image(d.bn, d.R, d.C, eh, ew, o), tan ? at::empty({d.bn, d.K, d.R, d.C}, o) : none(o), tan ? at::empty({d.bn, 3 * d.K, d.R, d.C}, o) : none(o)};
+}
 T3 sg_to_env_cuda(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, bool premap, bool want_tan) {
-  const auto dev = require_hip({&axis, &lamb, &weight});
+  const auto d = check_sg_to_env(axis, lamb, weight, eh, ew, true);
+  const auto dev = axis.device();
   const c10::DeviceGuard guard(dev);
+  auto [env, lam_t, w_t] = sg_to_env_outputs(d, eh, ew, premap && want_tan, axis.options());
   const Tensor a = axis.contiguous(), l = lamb.contiguous(), w = weight.contiguous();
-  const auto d = check_sg(a, l, w);
-  Tensor env = at::empty({d.bn, 3, d.R, d.C, eh, ew}, a.options());
-  const bool tan = premap && want_tan;
-  Tensor lam_t = tan ? at::empty_like(l) : none_like(l), w_t = tan ? at::empty_like(w) : none_like(w);
   const Tensor dirs = dirs_table(dev, eh, ew);
   ok(api().sgr_sg_to_env_fwd(rp(a), rp(l), rp(w), rp(dirs), wp(env), wp(lam_t), wp(w_t), (int)d.bn, (int)d.K, (int)d.R, (int)d.C, (int)eh, (int)ew,
                              premap ? 1 : 0, stream_of(dev)),
@@ -201,29 +198,29 @@ T3 sg_to_env_cuda(const Tensor& axis, const Tensor& lamb, const Tensor& weight, 
   return {env, lam_t, w_t};
 }
 T3 sg_to_env_meta(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, bool premap, bool want_tan) {
+  return sg_to_env_outputs(check_sg_to_env(axis, lamb, weight, eh, ew, false), eh, ew, premap && want_tan, axis.options());
+}
+SgDims check_sg_to_env_bwd(const Tensor& g_env, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, bool device) {
+  require_hip({&g_env, &axis, &lamb, &weight}, device);
   const auto d = check_sg(axis, lamb, weight);
-  const bool tan = premap && want_tan;
-  return {at::empty({d.bn, 3, d.R, d.C, eh, ew}, axis.options()), tan ? at::empty(lamb.sizes(), lamb.options()) : none_like(lamb),
-          tan ? at::empty(weight.sizes(), weight.options()) : none_like(weight)};
+  TORCH_CHECK(g_env.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C, eh, ew}), "sgrender: the env cotangent must be [bn,3,envRow,envCol,envHeight,envWidth]");
+  check_env_grid(eh, ew);
+  return d;
 }
 T3 sg_to_env_bwd_cuda(const Tensor& g_env, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, int64_t premap) {
-  const auto dev = require_hip({&g_env, &axis, &lamb, &weight});
+  const auto d = check_sg_to_env_bwd(g_env, axis, lamb, weight, eh, ew, true);
+  const auto dev = axis.device();
   const c10::DeviceGuard guard(dev);
+  auto [ga, gl, gw] = sg_like(d, axis.options());
   const Tensor g = g_env.contiguous(), a = axis.contiguous(), l = lamb.contiguous(), w = weight.contiguous();
-  const auto d = check_sg(a, l, w);
-  TORCH_CHECK(g.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C, eh, ew}), "sgrender: the env cotangent must be [bn,3,envRow,envCol,envHeight,envWidth]");
-  Tensor ga = at::empty_like(a), gl = at::empty_like(l), gw = at::empty_like(w);
   const Tensor dirs = dirs_table(dev, eh, ew);
   ok(api().sgr_sg_to_env_bwd(rp(g), rp(a), rp(l), rp(w), rp(dirs), wp(ga), wp(gl), wp(gw), (int)d.bn, (int)d.K, (int)d.R, (int)d.C, (int)eh, (int)ew,
                              (int)premap, stream_of(dev)),
      "sgr_sg_to_env_bwd");
   return {ga, gl, gw};
 }
-T3 like3_meta(const Tensor& a, const Tensor& l, const Tensor& w) {
-  return {at::empty(a.sizes(), a.options()), at::empty(l.sizes(), l.options()), at::empty(w.sizes(), w.options())};
-}
-T3 sg_to_env_bwd_meta(const Tensor&, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t, int64_t, int64_t) {
-  return like3_meta(axis, lamb, weight);
+T3 sg_to_env_bwd_meta(const Tensor& g_env, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, int64_t) {
+  return sg_like(check_sg_to_env_bwd(g_env, axis, lamb, weight, eh, ew, false), axis.options());
 }
 
 struct SgToEnvFn : public torch::autograd::Function<SgToEnvFn> {
@@ -278,67 +275,90 @@ T3 sg_to_env_autograd(const Tensor& axis, const Tensor& lamb, const Tensor& weig
 // ==================================================================================================================
 // env image -> (diffuse, specular)
 // ==================================================================================================================
+struct RenderDims { BrdfDims b; int64_t R, C; };
+RenderDims check_render_env(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& env, Cam cam, bool device) {
+  require_hip({&albedo, &normal, &rough, &env}, device);
+  const auto b = check_brdf(albedo, normal, rough);
+  TORCH_CHECK(env.dim() == 6 && env.size(0) == b.bn && env.size(1) == 3, "sgrender: envmap must be [bn,3,envRow,envCol,envHeight,envWidth], got ", env.sizes());
+  check_tables(env.size(4), env.size(5), cam);
+  return {b, env.size(2), env.size(3)};
+}
+T2 render_outputs(int64_t bn, int64_t R, int64_t C, const at::TensorOptions& o) { return {rgb(bn, R, C, o), rgb(bn, R, C, o)}; }      // diffuse, specular
 T2 render_env_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& env, double fov, double F0, Cam cam) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &env});
+  const auto [b, R, C] = check_render_env(albedo, normal, rough, env, cam, true);
+  const auto dev = albedo.device();
   const c10::DeviceGuard guard(dev);
+  auto [diffuse, spec] = render_outputs(b.bn, R, C, albedo.options());
   const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), e = env.contiguous();
-  const auto b = check_brdf(a, n, r);
-  TORCH_CHECK(e.dim() == 6 && e.size(0) == b.bn && e.size(1) == 3, "sgrender: envmap must be [bn,3,envRow,envCol,envHeight,envWidth], got ", e.sizes());
-  const int64_t R = e.size(2), C = e.size(3), eh = e.size(4), ew = e.size(5);
-  Tensor diffuse = at::empty({b.bn, 3, R, C}, a.options()), spec = at::empty({b.bn, 3, R, C}, a.options());
+  const int64_t eh = e.size(4), ew = e.size(5);
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, R, C, fov, cam);
   ok(api().sgr_render_env_fwd(rp(a), rp(n), rp(r), rp(e), rp(dirs), rp(view), wp(diffuse), wp(spec), (int)b.bn, (int)R, (int)C, (int)eh, (int)ew, (int)b.h,
                               (int)b.w, (float)F0, stream_of(dev)),
      "sgr_render_env_fwd");
   return {diffuse, spec};
 }
-T2 render_env_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& env, double, double, Cam) {
+T2 render_env_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& env, double, double, Cam cam) {
+  const auto d = check_render_env(albedo, normal, rough, env, cam, false);
+  return render_outputs(d.b.bn, d.R, d.C, albedo.options());
+}
+RenderDims check_render_env_bwd_env(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, int64_t eh,
+                                    int64_t ew, Cam cam, bool device) {
+  require_hip({&g_diffuse, &g_spec, &albedo, &normal, &rough}, device);
   const auto b = check_brdf(albedo, normal, rough);
-  TORCH_CHECK(env.dim() == 6, "sgrender: envmap must be 6-D");
-  return {at::empty({b.bn, 3, env.size(2), env.size(3)}, albedo.options()), at::empty({b.bn, 3, env.size(2), env.size(3)}, albedo.options())};
+  TORCH_CHECK(g_diffuse.dim() == 4 && g_diffuse.sizes() == g_spec.sizes() && g_diffuse.size(0) == b.bn && g_diffuse.size(1) == 3,
+              "sgrender: cotangents must be [bn,3,envRow,envCol]");
+  check_tables(eh, ew, cam);
+  return {b, g_diffuse.size(2), g_diffuse.size(3)};
 }
 Tensor render_env_bwd_env_cuda(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, int64_t eh,
                                int64_t ew, double fov, double F0, Cam cam) {
-  const auto dev = require_hip({&g_diffuse, &g_spec, &albedo, &normal, &rough});
+  const auto [b, R, C] = check_render_env_bwd_env(g_diffuse, g_spec, albedo, normal, rough, eh, ew, cam, true);
+  const auto dev = albedo.device();
   const c10::DeviceGuard guard(dev);
+  Tensor g_env = env_image(b.bn, R, C, eh, ew, albedo.options());
   const Tensor gd = g_diffuse.contiguous(), gs = g_spec.contiguous(), a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous();
-  const auto b = check_brdf(a, n, r);
-  TORCH_CHECK(gd.dim() == 4 && gd.sizes() == gs.sizes() && gd.size(0) == b.bn && gd.size(1) == 3, "sgrender: cotangents must be [bn,3,envRow,envCol]");
-  const int64_t R = gd.size(2), C = gd.size(3);
-  Tensor g_env = at::empty({b.bn, 3, R, C, eh, ew}, a.options());
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, R, C, fov, cam);
   ok(api().sgr_render_env_bwd_env(rp(gd), rp(gs), rp(a), rp(n), rp(r), rp(dirs), rp(view), wp(g_env), (int)b.bn, (int)R, (int)C, (int)eh, (int)ew, (int)b.h,
                                   (int)b.w, (float)F0, stream_of(dev)),
      "sgr_render_env_bwd_env");
   return g_env;
 }
-Tensor render_env_bwd_env_meta(const Tensor& g_diffuse, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t eh, int64_t ew, double, double, Cam) {
-  return at::empty({g_diffuse.size(0), 3, g_diffuse.size(2), g_diffuse.size(3), eh, ew}, g_diffuse.options());
+Tensor render_env_bwd_env_meta(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, int64_t eh, int64_t ew,
+                               double, double, Cam cam) {
+  const auto d = check_render_env_bwd_env(g_diffuse, g_spec, albedo, normal, rough, eh, ew, cam, false);
+  return env_image(d.b.bn, d.R, d.C, eh, ew, albedo.options());
+}
+// the light comes as the env image or, without one, as the SG parameters (K lobes; 0 with the image)
+struct BrdfBwdDims { BrdfDims b; int64_t R, C, K; };
+BrdfBwdDims check_render_bwd_brdf(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const OptTensor& env,
+                                  const OptTensor& axis, const OptTensor& lamb, const OptTensor& weight, int64_t eh, int64_t ew, Cam cam, bool device) {
+  require_hip({&g_diffuse, &g_spec, &albedo, &normal, &rough, opt(env), opt(axis), opt(lamb), opt(weight)}, device);
+  TORCH_CHECK(opt(env) || (opt(axis) && opt(lamb) && opt(weight)), "sgrender: render_bwd_brdf needs the env image or the SG parameters");
+  const auto b = check_brdf(albedo, normal, rough);
+  TORCH_CHECK(g_diffuse.dim() == 4 && g_diffuse.sizes() == g_spec.sizes() && g_diffuse.size(0) == b.bn, "sgrender: cotangents must be [bn,3,envRow,envCol]");
+  check_tables(eh, ew, cam);
+  return {b, g_diffuse.size(2), g_diffuse.size(3), opt(env) ? 0 : axis->size(1)};
 }
 T3 render_bwd_brdf_cuda(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const OptTensor& env,
                         const OptTensor& axis, const OptTensor& lamb, const OptTensor& weight, int64_t eh, int64_t ew, double fov, double F0, Cam cam,
                         bool premap) {
-  const auto dev = require_hip({&g_diffuse, &g_spec, &albedo, &normal, &rough, opt(env), opt(axis), opt(lamb), opt(weight)});
+  const auto [b, R, C, K] = check_render_bwd_brdf(g_diffuse, g_spec, albedo, normal, rough, env, axis, lamb, weight, eh, ew, cam, true);
+  const auto dev = albedo.device();
   const c10::DeviceGuard guard(dev);
+  auto [ga, gn, gr] = brdf_like(b, albedo.options());
   const Tensor gd = g_diffuse.contiguous(), gs = g_spec.contiguous(), a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous();
-  const bool have_env = opt(env) != nullptr;
-  TORCH_CHECK(have_env || (opt(axis) && opt(lamb) && opt(weight)), "sgrender: render_bwd_brdf needs the env image or the SG parameters");
   Tensor e, ax, la, we;
-  if (have_env) e = env->contiguous();
+  if (opt(env)) e = env->contiguous();
   else { ax = axis->contiguous(); la = lamb->contiguous(); we = weight->contiguous(); }
-  const auto b = check_brdf(a, n, r);
-  TORCH_CHECK(gd.dim() == 4 && gd.sizes() == gs.sizes() && gd.size(0) == b.bn, "sgrender: cotangents must be [bn,3,envRow,envCol]");
-  const int64_t R = gd.size(2), C = gd.size(3), K = have_env ? 0 : ax.size(1);
-  Tensor ga = at::empty_like(a), gn = at::empty_like(n), gr = at::empty_like(r);
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, R, C, fov, cam);
   ok(api().sgr_render_bwd_brdf(rp(gd), rp(gs), rp(a), rp(n), rp(r), rp(e), rp(ax), rp(la), rp(we), rp(dirs), rp(view), wp(ga), wp(gn), wp(gr), (int)b.bn,
                                (int)K, (int)R, (int)C, (int)eh, (int)ew, (int)b.h, (int)b.w, (float)F0, premap ? 1 : 0, stream_of(dev)),
      "sgr_render_bwd_brdf");
   return {ga, gn, gr};
 }
-T3 render_bwd_brdf_meta(const Tensor&, const Tensor&, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const OptTensor&, const OptTensor&,
-                        const OptTensor&, const OptTensor&, int64_t, int64_t, double, double, Cam, bool) {
-  return like3_meta(albedo, normal, rough);
+T3 render_bwd_brdf_meta(const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const OptTensor& env,
+                        const OptTensor& axis, const OptTensor& lamb, const OptTensor& weight, int64_t eh, int64_t ew, double, double, Cam cam, bool) {
+  return brdf_like(check_render_bwd_brdf(g_diffuse, g_spec, albedo, normal, rough, env, axis, lamb, weight, eh, ew, cam, false).b, albedo.options());
 }
 
 using BrdfBwdSig = T3(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
@@ -394,20 +414,29 @@ T2 render_env_autograd(const Tensor& albedo, const Tensor& normal, const Tensor&
 // ==================================================================================================================
 // fused: SG -> (env image), diffuse, specular                                     wrapperBRDFLight.py:177 + :194
 // ==================================================================================================================
-T5 fused_render_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh,
-                     int64_t ew, double fov, double F0, Cam cam, int64_t premap, bool need_env, bool want_tan) {
-  const auto dev = require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight});
-  const c10::DeviceGuard guard(dev);
-  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous();
-  const Tensor ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const auto d = check_sg(ax, la, we);
-  const auto b = check_brdf(a, n, r);
+struct FusedDims { SgDims d; BrdfDims b; };
+FusedDims check_fused_render(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh,
+                             int64_t ew, Cam cam, int64_t premap, bool device) {
+  require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight}, device);
+  const auto d = check_sg(axis, lamb, weight);
+  const auto b = check_brdf(albedo, normal, rough);
   TORCH_CHECK(b.bn == d.bn, "sgrender: BRDF maps and SG parameters disagree on the batch size");
   TORCH_CHECK(premap == 0 || premap == 1 || premap == 3, "sgrender: fused_render premap must be 0 (post-tan), 1 (decoder outputs in [0, 1]) or 3 (raw decoder outputs)");
-  Tensor env = need_env ? at::empty({d.bn, 3, d.R, d.C, eh, ew}, a.options()) : none_like(a);
-  Tensor diffuse = at::empty({d.bn, 3, d.R, d.C}, a.options()), spec = at::empty({d.bn, 3, d.R, d.C}, a.options());
-  const bool tan = premap == 1 && want_tan;
-  Tensor lam_t = tan ? at::empty_like(la) : none_like(la), w_t = tan ? at::empty_like(we) : none_like(we);
+  check_tables(eh, ew, cam);
+  return {d, b};
+}
+T5 fused_render_outputs(const SgDims& d, int64_t eh, int64_t ew, bool need_env, bool tan, const at::TensorOptions& o) {
+  return {need_env ? env_image(d.bn, d.R, d.C, eh, ew, o) : none(o), rgb(d.bn, d.R, d.C, o), rgb(d.bn, d.R, d.C, o),
+          tan ? at::empty({d.bn, d.K, d.R, d.C}, o) : none(o), tan ? at::empty({d.bn, 3 * d.K, d.R, d.C}, o) : none(o)};
+}
+T5 fused_render_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh,
+                     int64_t ew, double fov, double F0, Cam cam, int64_t premap, bool need_env, bool want_tan) {
+  const auto [d, b] = check_fused_render(albedo, normal, rough, axis, lamb, weight, eh, ew, cam, premap, true);
+  const auto dev = albedo.device();
+  const c10::DeviceGuard guard(dev);
+  auto [env, diffuse, spec, lam_t, w_t] = fused_render_outputs(d, eh, ew, need_env, premap == 1 && want_tan, albedo.options());
+  const Tensor a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous();
+  const Tensor ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
   ok(api().sgr_fused_fwd_tan(rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), wp(env), wp(lam_t), wp(w_t), wp(diffuse), wp(spec), (int)d.bn,
                              (int)d.K, (int)d.R, (int)d.C, (int)eh, (int)ew, (int)b.h, (int)b.w, (float)F0, (int)premap, stream_of(dev)),
@@ -415,36 +444,40 @@ T5 fused_render_cuda(const Tensor& albedo, const Tensor& normal, const Tensor& r
   return {env, diffuse, spec, lam_t, w_t};
 }
 T5 fused_render_meta(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh,
-                     int64_t ew, double, double, Cam, int64_t premap, bool need_env, bool want_tan) {
+                     int64_t ew, double, double, Cam cam, int64_t premap, bool need_env, bool want_tan) {
+  const auto d = check_fused_render(albedo, normal, rough, axis, lamb, weight, eh, ew, cam, premap, false).d;
+  return fused_render_outputs(d, eh, ew, need_env, premap == 1 && want_tan, albedo.options());
+}
+FusedDims check_fused_render_bwd_sg(const OptTensor& g_env, const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough,
+                                    const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, Cam cam, bool device) {
+  require_hip({opt(g_env), &g_diffuse, &g_spec, &albedo, &normal, &rough, &axis, &lamb, &weight}, device);
   const auto d = check_sg(axis, lamb, weight);
-  check_brdf(albedo, normal, rough);
-  const bool tan = premap == 1 && want_tan;
-  return {need_env ? at::empty({d.bn, 3, d.R, d.C, eh, ew}, albedo.options()) : none_like(albedo), at::empty({d.bn, 3, d.R, d.C}, albedo.options()),
-          at::empty({d.bn, 3, d.R, d.C}, albedo.options()), tan ? at::empty(lamb.sizes(), lamb.options()) : none_like(lamb),
-          tan ? at::empty(weight.sizes(), weight.options()) : none_like(weight)};
+  const auto b = check_brdf(albedo, normal, rough);
+  TORCH_CHECK(g_diffuse.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C}) && g_spec.sizes() == g_diffuse.sizes(),
+              "sgrender: diffuse / specular cotangents must be [bn,3,envRow,envCol]");
+  TORCH_CHECK(!opt(g_env) || (*g_env).sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C, eh, ew}), "sgrender: the env cotangent must be [bn,3,envRow,envCol,envHeight,envWidth]");
+  check_tables(eh, ew, cam);
+  return {d, b};
 }
 T3 fused_render_bwd_sg_cuda(const OptTensor& g_env, const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough,
                             const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, double fov, double F0, Cam cam, int64_t premap) {
-  const auto dev = require_hip({opt(g_env), &g_diffuse, &g_spec, &albedo, &normal, &rough, &axis, &lamb, &weight});
+  const auto [d, b] = check_fused_render_bwd_sg(g_env, g_diffuse, g_spec, albedo, normal, rough, axis, lamb, weight, eh, ew, cam, true);
+  const auto dev = albedo.device();
   const c10::DeviceGuard guard(dev);
+  auto [ga, gl, gw] = sg_like(d, axis.options());
   Tensor ge;
   if (opt(g_env)) ge = g_env->contiguous();
   const Tensor gd = g_diffuse.contiguous(), gs = g_spec.contiguous(), a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous();
   const Tensor ax = axis.contiguous(), la = lamb.contiguous(), we = weight.contiguous();
-  const auto d = check_sg(ax, la, we);
-  const auto b = check_brdf(a, n, r);
-  TORCH_CHECK(gd.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C}) && gs.sizes() == gd.sizes(), "sgrender: diffuse / specular cotangents must be [bn,3,envRow,envCol]");
-  TORCH_CHECK(!ge.defined() || ge.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C, eh, ew}), "sgrender: the env cotangent must be [bn,3,envRow,envCol,envHeight,envWidth]");
-  Tensor ga = at::empty_like(ax), gl = at::empty_like(la), gw = at::empty_like(we);
   const Tensor dirs = dirs_table(dev, eh, ew), view = view_table(dev, d.R, d.C, fov, cam);
   ok(api().sgr_fused_bwd_sg(rp(ge), rp(gd), rp(gs), rp(a), rp(n), rp(r), rp(ax), rp(la), rp(we), rp(dirs), rp(view), wp(ga), wp(gl), wp(gw), (int)d.bn,
                             (int)d.K, (int)d.R, (int)d.C, (int)eh, (int)ew, (int)b.h, (int)b.w, (float)F0, (int)premap, stream_of(dev)),
      "sgr_fused_bwd_sg");
   return {ga, gl, gw};
 }
-T3 fused_render_bwd_sg_meta(const OptTensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor& axis, const Tensor& lamb,
-                            const Tensor& weight, int64_t, int64_t, double, double, Cam, int64_t) {
-  return like3_meta(axis, lamb, weight);
+T3 fused_render_bwd_sg_meta(const OptTensor& g_env, const Tensor& g_diffuse, const Tensor& g_spec, const Tensor& albedo, const Tensor& normal, const Tensor& rough,
+                            const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, double, double, Cam cam, int64_t) {
+  return sg_like(check_fused_render_bwd_sg(g_env, g_diffuse, g_spec, albedo, normal, rough, axis, lamb, weight, eh, ew, cam, false).d, axis.options());
 }
 
 struct FusedRenderFn : public torch::autograd::Function<FusedRenderFn> {
@@ -517,76 +550,95 @@ T5 fused_render_autograd(const Tensor& albedo, const Tensor& normal, const Tenso
 // ==================================================================================================================
 Tensor loss_workspace(int64_t bn, const Tensor& like) { return at::empty({api().sgr_loss_workspace_floats((int)bn)}, like.options()); }
 
+int64_t check_lsregress_coef(const Tensor& pred, const Tensor& gt, bool device) {
+  require_hip({&pred, &gt}, device);
+  TORCH_CHECK(pred.dim() >= 1 && pred.sizes() == gt.sizes(), "sgrender: LSregress needs pred and gt of one shape");
+  return pred.size(0);
+}
 Tensor lsregress_coef_cuda(const Tensor& pred, const Tensor& gt) {
-  const auto dev = require_hip({&pred, &gt});
-  const c10::DeviceGuard guard(dev);
+  const int64_t nb = check_lsregress_coef(pred, gt, true);
+  const c10::DeviceGuard guard(pred.device());
+  Tensor coef = at::empty({nb}, pred.options()), ws = loss_workspace(nb, pred);
   const Tensor p = pred.contiguous(), g = gt.contiguous();
-  TORCH_CHECK(p.dim() >= 1 && p.sizes() == g.sizes(), "sgrender: LSregress needs pred and gt of one shape");
-  const int64_t nb = p.size(0);
-  Tensor coef = at::empty({nb}, p.options()), ws = loss_workspace(nb, p);
-  ok(api().sgr_lsregress_coef(rp(p), rp(g), wp(coef), wp(ws), (int)nb, (long long)(p.numel() / nb), stream_of(dev)), "sgr_lsregress_coef");
+  ok(api().sgr_lsregress_coef(rp(p), rp(g), wp(coef), wp(ws), (int)nb, (long long)(p.numel() / nb), stream_of(pred.device())), "sgr_lsregress_coef");
   return coef;
 }
-Tensor lsregress_coef_meta(const Tensor& pred, const Tensor&) { return at::empty({pred.size(0)}, pred.options()); }
+Tensor lsregress_coef_meta(const Tensor& pred, const Tensor& gt) { return at::empty({check_lsregress_coef(pred, gt, false)}, pred.options()); }
+int64_t check_lsregress_diffspec_coef(const Tensor& diff, const Tensor& spec, const Tensor& im, bool device) {
+  require_hip({&diff, &spec, &im}, device);
+  TORCH_CHECK(diff.sizes() == spec.sizes() && diff.sizes() == im.sizes(), "sgrender: LSregressDiffSpec needs diff, spec and imOrig of one shape");
+  return diff.size(0);
+}
 Tensor lsregress_diffspec_coef_cuda(const Tensor& diff, const Tensor& spec, const Tensor& im) {
-  const auto dev = require_hip({&diff, &spec, &im});
-  const c10::DeviceGuard guard(dev);
+  const int64_t nb = check_lsregress_diffspec_coef(diff, spec, im, true);
+  const c10::DeviceGuard guard(diff.device());
+  Tensor coef = at::empty({nb, 2}, diff.options()), ws = loss_workspace(nb, diff);
   const Tensor d = diff.contiguous(), s = spec.contiguous(), i = im.contiguous();
-  TORCH_CHECK(d.sizes() == s.sizes() && d.sizes() == i.sizes(), "sgrender: LSregressDiffSpec needs diff, spec and imOrig of one shape");
-  const int64_t nb = d.size(0);
-  Tensor coef = at::empty({nb, 2}, d.options()), ws = loss_workspace(nb, d);
-  ok(api().sgr_lsregress_diffspec_coef(rp(d), rp(s), rp(i), wp(coef), wp(ws), (int)nb, (int)(d.numel() / nb), stream_of(dev)), "sgr_lsregress_diffspec_coef");
+  ok(api().sgr_lsregress_diffspec_coef(rp(d), rp(s), rp(i), wp(coef), wp(ws), (int)nb, (int)(d.numel() / nb), stream_of(diff.device())), "sgr_lsregress_diffspec_coef");
   return coef;
 }
-Tensor lsregress_diffspec_coef_meta(const Tensor& diff, const Tensor&, const Tensor&) { return at::empty({diff.size(0), 2}, diff.options()); }
+Tensor lsregress_diffspec_coef_meta(const Tensor& diff, const Tensor& spec, const Tensor& im) {
+  return at::empty({check_lsregress_diffspec_coef(diff, spec, im, false), 2}, diff.options());
+}
 
 // render_loss(diffuse, spec, im, seg, R, C, total) -> (loss, scale, parts, rendered, im_small, seg_small, coef)
 //   total = true  (one rank):  loss = renderErr, scale = d loss / d numerator; three launches (the third pass forms the value)
 //   total = false (sharded):   loss / scale empty; parts = (numerator, raw denominator) of this shard, all-reduced by the caller
 // differentiable outputs: loss (total) or parts (sharded; only its numerator carries a gradient)
-T7 render_loss_cuda(const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C, bool total) {
-  const auto dev = require_hip({&diffuse, &spec, &im, &seg});
-  const c10::DeviceGuard guard(dev);
-  const Tensor d = diffuse.contiguous(), s = spec.contiguous(), i = im.contiguous(), g = seg.contiguous();
-  TORCH_CHECK(d.dim() == 4, "sgrender: diffuse/spec must be [bn,3,", R, ",", C, "]");
-  const int64_t bn = d.size(0);
-  TORCH_CHECK(d.sizes() == at::IntArrayRef({bn, 3, R, C}) && s.sizes() == d.sizes(), "sgrender: diffuse/spec must be [bn,3,", R, ",", C, "]");
-  TORCH_CHECK(i.dim() == 4 && i.size(0) == bn && i.size(1) == 3 && g.sizes() == at::IntArrayRef({bn, 1, i.size(2), i.size(3)}),
+struct LossDims { int64_t bn, imH, imW; };
+LossDims check_render_loss(const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C, bool device) {
+  require_hip({&diffuse, &spec, &im, &seg}, device);
+  TORCH_CHECK(diffuse.dim() == 4, "sgrender: diffuse/spec must be [bn,3,", R, ",", C, "]");
+  const int64_t bn = diffuse.size(0);
+  TORCH_CHECK(diffuse.sizes() == at::IntArrayRef({bn, 3, R, C}) && spec.sizes() == diffuse.sizes(), "sgrender: diffuse/spec must be [bn,3,", R, ",", C, "]");
+  TORCH_CHECK(im.dim() == 4 && im.size(0) == bn && im.size(1) == 3 && seg.sizes() == at::IntArrayRef({bn, 1, im.size(2), im.size(3)}),
               "sgrender: im must be [bn,3,h,w] and seg [bn,1,h,w]");
-  const int64_t imH = i.size(2), imW = i.size(3);
-  const auto o = d.options();
-  Tensor im_s = at::empty({bn, 3, R, C}, o), seg_s = at::empty({bn, 1, R, C}, o), rendered = at::empty({bn, 3, R, C}, o), coef = at::empty({bn, 2}, o);
-  Tensor parts = at::empty({2}, o), ws = loss_workspace(bn, d);
-  Tensor loss = total ? at::empty({}, o) : none_like(d), scale = total ? at::empty({1}, o) : none_like(d);      // separate buffers: no shared version counter
+  return {bn, im.size(2), im.size(3)};
+}
+// (loss, scale, parts, rendered, im_small, seg_small, coef); loss and scale are separate buffers: no shared version counter
+T7 render_loss_outputs(int64_t bn, int64_t R, int64_t C, bool total, const at::TensorOptions& o) {
+  return {total ? at::empty({}, o) : none(o), total ? at::empty({1}, o) : none(o), at::empty({2}, o), rgb(bn, R, C, o), rgb(bn, R, C, o), at::empty({bn, 1, R, C}, o),
+          at::empty({bn, 2}, o)};
+}
+T7 render_loss_cuda(const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C, bool total) {
+  const auto [bn, imH, imW] = check_render_loss(diffuse, spec, im, seg, R, C, true);
+  const c10::DeviceGuard guard(diffuse.device());
+  auto [loss, scale, parts, rendered, im_s, seg_s, coef] = render_loss_outputs(bn, R, C, total, diffuse.options());
+  Tensor ws = loss_workspace(bn, diffuse);
+  const Tensor d = diffuse.contiguous(), s = spec.contiguous(), i = im.contiguous(), g = seg.contiguous();
   ok(api().sgr_render_loss_fwd_total(rp(d), rp(s), rp(i), rp(g), wp(im_s), wp(seg_s), wp(rendered), wp(coef), wp(parts), total ? loss.data_ptr<float>() : nullptr,
-                                     wp(scale), 3.0f, wp(ws), (int)bn, (int)R, (int)C, (int)imH, (int)imW, stream_of(dev)),
+                                     wp(scale), 3.0f, wp(ws), (int)bn, (int)R, (int)C, (int)imH, (int)imW, stream_of(diffuse.device())),
      "sgr_render_loss_fwd");
   return {loss, scale, parts, rendered, im_s, seg_s, coef};
 }
-T7 render_loss_meta(const Tensor& diffuse, const Tensor&, const Tensor&, const Tensor&, int64_t R, int64_t C, bool total) {
-  const int64_t bn = diffuse.size(0);
-  const auto o = diffuse.options();
-  return {total ? at::empty({}, o) : none_like(diffuse), total ? at::empty({1}, o) : none_like(diffuse), at::empty({2}, o), at::empty({bn, 3, R, C}, o),
-          at::empty({bn, 3, R, C}, o), at::empty({bn, 1, R, C}, o), at::empty({bn, 2}, o)};
+T7 render_loss_meta(const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C, bool total) {
+  return render_loss_outputs(check_render_loss(diffuse, spec, im, seg, R, C, false).bn, R, C, total, diffuse.options());
 }
 // g_loss (device scalar, nullable = 1) * weight * scale (device scalar, nullable = 1) * d numerator / d{diffuse, spec}
+void check_render_loss_bwd(const OptTensor& g_loss, const OptTensor& scale, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s, const Tensor& seg_s,
+                           const Tensor& coef, bool device) {
+  require_hip({opt(g_loss), opt(scale), &diffuse, &spec, &im_s, &seg_s, &coef}, device);
+  TORCH_CHECK(diffuse.dim() == 4 && spec.sizes() == diffuse.sizes() && im_s.sizes() == diffuse.sizes(), "sgrender: render_loss_bwd shapes disagree");
+}
+T2 render_loss_bwd_outputs(const Tensor& diffuse) { return {at::empty(diffuse.sizes(), diffuse.options()), at::empty(diffuse.sizes(), diffuse.options())}; }
 T2 render_loss_bwd_cuda(const OptTensor& g_loss, double weight, const OptTensor& scale, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s,
                         const Tensor& seg_s, const Tensor& coef) {
-  const auto dev = require_hip({opt(g_loss), opt(scale), &diffuse, &spec, &im_s, &seg_s, &coef});
-  const c10::DeviceGuard guard(dev);
+  check_render_loss_bwd(g_loss, scale, diffuse, spec, im_s, seg_s, coef, true);
+  const c10::DeviceGuard guard(diffuse.device());
+  auto [gd, gs] = render_loss_bwd_outputs(diffuse);
   const Tensor d = diffuse.contiguous(), s = spec.contiguous(), i = im_s.contiguous(), g = seg_s.contiguous(), c = coef.contiguous();
   Tensor gl, sc;
   if (opt(g_loss)) gl = g_loss->contiguous();
   if (opt(scale)) sc = scale->contiguous();
-  TORCH_CHECK(d.dim() == 4 && s.sizes() == d.sizes() && i.sizes() == d.sizes(), "sgrender: render_loss_bwd shapes disagree");
-  Tensor gd = at::empty_like(d), gs = at::empty_like(s);
   ok(api().sgr_render_loss_bwd_scaled(rp(gl), (float)weight, rp(sc), rp(d), rp(s), rp(i), rp(g), rp(c), wp(gd), wp(gs), (int)d.size(0), (int)d.size(2),
-                                      (int)d.size(3), stream_of(dev)),
+                                      (int)d.size(3), stream_of(diffuse.device())),
      "sgr_render_loss_bwd");
   return {gd, gs};
 }
-T2 render_loss_bwd_meta(const OptTensor&, double, const OptTensor&, const Tensor& diffuse, const Tensor& spec, const Tensor&, const Tensor&, const Tensor&) {
-  return {at::empty(diffuse.sizes(), diffuse.options()), at::empty(spec.sizes(), spec.options())};
+T2 render_loss_bwd_meta(const OptTensor& g_loss, double, const OptTensor& scale, const Tensor& diffuse, const Tensor& spec, const Tensor& im_s, const Tensor& seg_s,
+                        const Tensor& coef) {
+  check_render_loss_bwd(g_loss, scale, diffuse, spec, im_s, seg_s, coef, false);
+  return render_loss_bwd_outputs(diffuse);
 }
 struct RenderLossFn : public torch::autograd::Function<RenderLossFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& diffuse, const Tensor& spec, const Tensor& im, const Tensor& seg, int64_t R, int64_t C,
@@ -631,17 +683,22 @@ T7 render_loss_autograd(const Tensor& diffuse, const Tensor& spec, const Tensor&
 // sits here -- its backward is the render-loss backward kernel with the GLOBAL normaliser (scale = d loss / d numerator), so every rank
 // gets the gradient of the global loss w.r.t. its shard.  (diffuse / spec / im_small / seg_small / coef: what render_loss(total = False)
 // took and returned for this shard.)  Five launches and one collective per step, as in rounds 2-3.
-T2 render_loss_finalize_cuda(const Tensor& diffuse, const Tensor& spec, const Tensor& parts, const Tensor& im_s, const Tensor& seg_s, const Tensor& coef) {
-  const auto dev = require_hip({&diffuse, &spec, &parts, &im_s, &seg_s, &coef});
-  const c10::DeviceGuard guard(dev);
-  const Tensor p = parts.contiguous();
-  TORCH_CHECK(p.numel() == 2, "sgrender: render_loss_finalize takes the two totals [numerator, denominator]");
-  Tensor loss = at::empty({}, p.options()), scale = at::empty({1}, p.options());
-  ok(api().sgr_loss_finalize(rp(p), loss.data_ptr<float>(), wp(scale), 3.0f, stream_of(dev)), "sgr_loss_finalize");
-  return {loss, scale};
+void check_render_loss_finalize(const Tensor& diffuse, const Tensor& spec, const Tensor& parts, const Tensor& im_s, const Tensor& seg_s, const Tensor& coef, bool device) {
+  require_hip({&diffuse, &spec, &parts, &im_s, &seg_s, &coef}, device);
+  TORCH_CHECK(count(parts) == 2, "sgrender: render_loss_finalize takes the two totals [numerator, denominator]");
 }
-T2 render_loss_finalize_meta(const Tensor&, const Tensor&, const Tensor& parts, const Tensor&, const Tensor&, const Tensor&) {
-  return {at::empty({}, parts.options()), at::empty({1}, parts.options())};
+T2 loss_and_scale(const at::TensorOptions& o) { return {at::empty({}, o), at::empty({1}, o)}; }
+T2 render_loss_finalize_cuda(const Tensor& diffuse, const Tensor& spec, const Tensor& parts, const Tensor& im_s, const Tensor& seg_s, const Tensor& coef) {
+  check_render_loss_finalize(diffuse, spec, parts, im_s, seg_s, coef, true);
+  const c10::DeviceGuard guard(diffuse.device());
+  T2 out = loss_and_scale(parts.options());
+  const Tensor p = parts.contiguous();
+  ok(api().sgr_loss_finalize(rp(p), std::get<0>(out).data_ptr<float>(), wp(std::get<1>(out)), 3.0f, stream_of(diffuse.device())), "sgr_loss_finalize");
+  return out;
+}
+T2 render_loss_finalize_meta(const Tensor& diffuse, const Tensor& spec, const Tensor& parts, const Tensor& im_s, const Tensor& seg_s, const Tensor& coef) {
+  check_render_loss_finalize(diffuse, spec, parts, im_s, seg_s, coef, false);
+  return loss_and_scale(parts.options());
 }
 struct RenderLossFinalizeFn : public torch::autograd::Function<RenderLossFinalizeFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& diffuse, const Tensor& spec, const Tensor& parts, const Tensor& im_s, const Tensor& seg_s,
@@ -677,38 +734,49 @@ T2 render_loss_finalize_autograd(const Tensor& diffuse, const Tensor& spec, cons
 // ==================================================================================================================
 // env reconstruction loss, unfused (two streaming passes over a materialised env image)      wrapperBRDFLight.py:172-188
 // ==================================================================================================================
+struct EnvDims { int64_t bn, R, C, eh, ew; };
+EnvDims check_recon_loss_parts(const Tensor& env, const Tensor& env_gt, const Tensor& seg_small, const Tensor& env_ind, bool device) {
+  require_hip({&env, &env_gt, &seg_small, &env_ind}, device);
+  TORCH_CHECK(env.dim() == 6 && env.sizes() == env_gt.sizes() && env.size(1) == 3, "sgrender: envmapsPred / envmaps must both be [bn,3,envRow,envCol,envHeight,envWidth]");
+  const EnvDims d{env.size(0), env.size(2), env.size(3), env.size(4), env.size(5)};
+  TORCH_CHECK(count(seg_small) == d.bn * d.R * d.C && count(env_ind) == d.bn, "sgrender: the pooled object mask must be [bn,1,envRow,envCol] and envmapsInd [bn,...]");
+  return d;
+}
+T3 recon_loss_parts_outputs(const EnvDims& d, const at::TensorOptions& o) { return {at::empty({2}, o), at::empty({d.bn, d.R * d.C}, o), at::empty({d.bn}, o)}; }      // parts, mask, coef
 T3 recon_loss_parts_cuda(const Tensor& env, const Tensor& env_gt, const Tensor& seg_small, const Tensor& env_ind, double offset) {
-  const auto dev = require_hip({&env, &env_gt, &seg_small, &env_ind});
-  const c10::DeviceGuard guard(dev);
+  const auto d = check_recon_loss_parts(env, env_gt, seg_small, env_ind, true);
+  const c10::DeviceGuard guard(env.device());
+  auto [parts, mask, coef] = recon_loss_parts_outputs(d, env.options());
+  Tensor ws = at::empty({api().sgr_recon_workspace_floats((int)d.bn, (int)d.R, (int)d.C)}, env.options());
   const Tensor e = env.contiguous(), g = env_gt.contiguous();
-  TORCH_CHECK(e.dim() == 6 && e.sizes() == g.sizes() && e.size(1) == 3, "sgrender: envmapsPred / envmaps must both be [bn,3,envRow,envCol,envHeight,envWidth]");
-  const int64_t bn = e.size(0), R = e.size(2), C = e.size(3), eh = e.size(4), ew = e.size(5);
-  TORCH_CHECK(seg_small.numel() == bn * R * C && env_ind.numel() == bn, "sgrender: the pooled object mask must be [bn,1,envRow,envCol] and envmapsInd [bn,...]");
-  const Tensor sm = seg_small.contiguous().reshape({bn, R * C}), ind = env_ind.contiguous().reshape({bn});
-  const auto o = e.options();
-  Tensor mask = at::empty({bn, R * C}, o), coef = at::empty({bn}, o), parts = at::empty({2}, o);
-  Tensor ws = at::empty({api().sgr_recon_workspace_floats((int)bn, (int)R, (int)C)}, o);
-  ok(api().sgr_recon_loss_fwd(rp(e), rp(g), rp(sm), rp(ind), wp(mask), wp(coef), wp(parts), wp(ws), (int)bn, (int)R, (int)C, (int)eh, (int)ew, (float)offset,
-                              stream_of(dev)),
+  const Tensor sm = seg_small.contiguous().reshape({d.bn, d.R * d.C}), ind = env_ind.contiguous().reshape({d.bn});
+  ok(api().sgr_recon_loss_fwd(rp(e), rp(g), rp(sm), rp(ind), wp(mask), wp(coef), wp(parts), wp(ws), (int)d.bn, (int)d.R, (int)d.C, (int)d.eh, (int)d.ew, (float)offset,
+                              stream_of(env.device())),
      "sgr_recon_loss_fwd");
   return {parts, mask, coef};
 }
-T3 recon_loss_parts_meta(const Tensor& env, const Tensor&, const Tensor&, const Tensor&, double) {
-  const auto o = env.options();
-  return {at::empty({2}, o), at::empty({env.size(0), env.size(2) * env.size(3)}, o), at::empty({env.size(0)}, o)};
+T3 recon_loss_parts_meta(const Tensor& env, const Tensor& env_gt, const Tensor& seg_small, const Tensor& env_ind, double) {
+  return recon_loss_parts_outputs(check_recon_loss_parts(env, env_gt, seg_small, env_ind, false), env.options());
 }
+void check_recon_loss_bwd(const Tensor& g_num, const Tensor& env, const Tensor& env_gt, const Tensor& mask, const Tensor& coef, bool device) {
+  require_hip({&g_num, &env, &env_gt, &mask, &coef}, device);
+  TORCH_CHECK(env.dim() == 6 && env.sizes() == env_gt.sizes(), "sgrender: recon_loss_bwd shapes disagree");
+}
+Tensor recon_loss_bwd_output(const Tensor& env) { return at::empty(env.sizes(), env.options()); }
 Tensor recon_loss_bwd_cuda(const Tensor& g_num, const Tensor& env, const Tensor& env_gt, const Tensor& mask, const Tensor& coef, double offset) {
-  const auto dev = require_hip({&g_num, &env, &env_gt, &mask, &coef});
-  const c10::DeviceGuard guard(dev);
+  check_recon_loss_bwd(g_num, env, env_gt, mask, coef, true);
+  const c10::DeviceGuard guard(env.device());
+  Tensor g_env = recon_loss_bwd_output(env);
   const Tensor e = env.contiguous(), g = env_gt.contiguous(), m = mask.contiguous(), c = coef.contiguous(), gn = g_num.contiguous();
-  TORCH_CHECK(e.dim() == 6 && e.sizes() == g.sizes(), "sgrender: recon_loss_bwd shapes disagree");
-  Tensor g_env = at::empty_like(e);
   ok(api().sgr_recon_loss_bwd(rp(gn), rp(e), rp(g), rp(m), rp(c), wp(g_env), (int)e.size(0), (int)e.size(2), (int)e.size(3), (int)e.size(4), (int)e.size(5),
-                              (float)offset, stream_of(dev)),
+                              (float)offset, stream_of(env.device())),
      "sgr_recon_loss_bwd");
   return g_env;
 }
-Tensor recon_loss_bwd_meta(const Tensor&, const Tensor& env, const Tensor&, const Tensor&, const Tensor&, double) { return at::empty(env.sizes(), env.options()); }
+Tensor recon_loss_bwd_meta(const Tensor& g_num, const Tensor& env, const Tensor& env_gt, const Tensor& mask, const Tensor& coef, double) {
+  check_recon_loss_bwd(g_num, env, env_gt, mask, coef, false);
+  return recon_loss_bwd_output(env);
+}
 struct ReconLossFn : public torch::autograd::Function<ReconLossFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& env, const Tensor& env_gt, const Tensor& seg_small, const Tensor& env_ind, double offset) {
     T3 out;
@@ -740,8 +808,7 @@ T3 recon_loss_parts_autograd(const Tensor& env, const Tensor& env_gt, const Tens
 // ==================================================================================================================
 // decoder output heads                                                      models.py:336-346, wrapperBRDFLight.py:167-168
 // ==================================================================================================================
-struct HeadDims { int64_t bn, K, R, C; };
-HeadDims check_heads(const Tensor& xa, const Tensor& xl, const Tensor& xw) {
+SgDims check_heads(const Tensor& xa, const Tensor& xl, const Tensor& xw) {
   TORCH_CHECK(xa.dim() == 4 && xl.dim() == 4 && xw.dim() == 4 && xa.size(1) % 3 == 0,
               "sgrender: light_heads takes the three decoders' [bn,3K,R,C], [bn,K,R,C], [bn,3K,R,C] outputs");
   const int64_t bn = xa.size(0), K = xa.size(1) / 3, R = xa.size(2), C = xa.size(3);
@@ -749,43 +816,53 @@ HeadDims check_heads(const Tensor& xa, const Tensor& xl, const Tensor& xw) {
               ", ", xl.sizes(), ", ", xw.sizes());
   return {bn, K, R, C};
 }
+SgDims check_light_heads(const Tensor& xa, const Tensor& xl, const Tensor& xw, bool device) {
+  require_hip({&xa, &xl, &xw}, device);
+  return check_heads(xa, xl, xw);
+}
+T4 light_heads_outputs(const SgDims& d, bool need_packed, const at::TensorOptions& o) {      // axis, lamb, weight, packed
+  const auto [axis, lamb, weight] = sg_like(d, o);
+  return {axis, lamb, weight, need_packed ? at::empty({d.bn, 7 * d.K, d.R, d.C}, o) : none(o)};
+}
 T4 light_heads_cuda(const Tensor& xa, const Tensor& xl, const Tensor& xw, bool need_packed) {
-  const auto dev = require_hip({&xa, &xl, &xw});
-  const c10::DeviceGuard guard(dev);
+  const auto d = check_light_heads(xa, xl, xw, true);
+  const c10::DeviceGuard guard(xa.device());
+  auto [axis, lamb, weight, packed] = light_heads_outputs(d, need_packed, xa.options());
   const Tensor a = xa.contiguous(), l = xl.contiguous(), w = xw.contiguous();
-  const auto d = check_heads(a, l, w);
-  const auto o = a.options();
-  Tensor axis = at::empty({d.bn, d.K, 3, d.R, d.C}, o), lamb = at::empty({d.bn, d.K, d.R, d.C}, o), weight = at::empty({d.bn, 3 * d.K, d.R, d.C}, o);
-  Tensor packed = need_packed ? at::empty({d.bn, 7 * d.K, d.R, d.C}, o) : none_like(a);
-  ok(api().sgr_light_heads_fwd(rp(a), rp(l), rp(w), wp(axis), wp(lamb), wp(weight), wp(packed), (int)d.bn, (int)d.K, (int)d.R, (int)d.C, stream_of(dev)),
+  ok(api().sgr_light_heads_fwd(rp(a), rp(l), rp(w), wp(axis), wp(lamb), wp(weight), wp(packed), (int)d.bn, (int)d.K, (int)d.R, (int)d.C, stream_of(xa.device())),
      "sgr_light_heads_fwd");
   return {axis, lamb, weight, packed};
 }
 T4 light_heads_meta(const Tensor& xa, const Tensor& xl, const Tensor& xw, bool need_packed) {
-  const auto d = check_heads(xa, xl, xw);
-  const auto o = xa.options();
-  return {at::empty({d.bn, d.K, 3, d.R, d.C}, o), at::empty({d.bn, d.K, d.R, d.C}, o), at::empty({d.bn, 3 * d.K, d.R, d.C}, o),
-          need_packed ? at::empty({d.bn, 7 * d.K, d.R, d.C}, o) : none_like(xa)};
+  return light_heads_outputs(check_light_heads(xa, xl, xw, false), need_packed, xa.options());
+}
+SgDims check_light_heads_bwd(const Tensor& xa, const Tensor& xl, const Tensor& xw, const OptTensor& g_axis, const OptTensor& g_lamb, const OptTensor& g_weight,
+                               const OptTensor& g_packed, bool device) {
+  require_hip({&xa, &xl, &xw, opt(g_axis), opt(g_lamb), opt(g_weight), opt(g_packed)}, device);
+  return check_heads(xa, xl, xw);
+}
+T3 light_heads_bwd_outputs(const SgDims& d, const at::TensorOptions& o) {      // the gradients of x_axis, x_lamb, x_weight
+  return {at::empty({d.bn, 3 * d.K, d.R, d.C}, o), at::empty({d.bn, d.K, d.R, d.C}, o), at::empty({d.bn, 3 * d.K, d.R, d.C}, o)};
 }
 T3 light_heads_bwd_cuda(const Tensor& xa, const Tensor& xl, const Tensor& xw, const OptTensor& g_axis, const OptTensor& g_lamb, const OptTensor& g_weight,
                         const OptTensor& g_packed) {
-  const auto dev = require_hip({&xa, &xl, &xw, opt(g_axis), opt(g_lamb), opt(g_weight), opt(g_packed)});
-  const c10::DeviceGuard guard(dev);
+  const auto d = check_light_heads_bwd(xa, xl, xw, g_axis, g_lamb, g_weight, g_packed, true);
+  const c10::DeviceGuard guard(xa.device());
+  auto [gxa, gxl, gxw] = light_heads_bwd_outputs(d, xa.options());
   const Tensor a = xa.contiguous(), l = xl.contiguous(), w = xw.contiguous();
-  const auto d = check_heads(a, l, w);
   Tensor ga, gl, gw, gp;
   if (opt(g_axis)) ga = g_axis->contiguous();
   if (opt(g_lamb)) gl = g_lamb->contiguous();
   if (opt(g_weight)) gw = g_weight->contiguous();
   if (opt(g_packed)) gp = g_packed->contiguous();
-  Tensor gxa = at::empty_like(a), gxl = at::empty_like(l), gxw = at::empty_like(w);
   ok(api().sgr_light_heads_bwd(rp(a), rp(l), rp(w), rp(ga), rp(gl), rp(gw), rp(gp), wp(gxa), wp(gxl), wp(gxw), (int)d.bn, (int)d.K, (int)d.R, (int)d.C,
-                               stream_of(dev)),
+                               stream_of(xa.device())),
      "sgr_light_heads_bwd");
   return {gxa, gxl, gxw};
 }
-T3 light_heads_bwd_meta(const Tensor& xa, const Tensor& xl, const Tensor& xw, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&) {
-  return like3_meta(xa, xl, xw);
+T3 light_heads_bwd_meta(const Tensor& xa, const Tensor& xl, const Tensor& xw, const OptTensor& g_axis, const OptTensor& g_lamb, const OptTensor& g_weight,
+                        const OptTensor& g_packed) {
+  return light_heads_bwd_outputs(check_light_heads_bwd(xa, xl, xw, g_axis, g_lamb, g_weight, g_packed, false), xa.options());
 }
 struct LightHeadsFn : public torch::autograd::Function<LightHeadsFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& xa, const Tensor& xl, const Tensor& xw, bool need_packed) {
@@ -821,46 +898,60 @@ T4 light_heads_autograd(const Tensor& xa, const Tensor& xl, const Tensor& xw, bo
 // glue either side of the path (forward only)                utils.py:156-195, testReal.py:421-432, wrapperBRDFLight.py:138-156
 // ==================================================================================================================
 Tensor sg_shading_cuda(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, int64_t premap) {
-  const auto dev = require_hip({&axis, &lamb, &weight});
+  const auto d = check_sg_to_env(axis, lamb, weight, eh, ew, true);
+  const auto dev = axis.device();
   const c10::DeviceGuard guard(dev);
+  Tensor out = rgb(d.bn, d.R, d.C, axis.options());
   const Tensor a = axis.contiguous(), l = lamb.contiguous(), w = weight.contiguous();
-  const auto d = check_sg(a, l, w);
-  Tensor out = at::empty({d.bn, 3, d.R, d.C}, a.options());
   const Tensor dirs = dirs_table(dev, eh, ew);
   ok(api().sgr_sg_shading(rp(a), rp(l), rp(w), rp(dirs), wp(out), (int)d.bn, (int)d.K, (int)d.R, (int)d.C, (int)eh, (int)ew, (int)premap, stream_of(dev)), "sgr_sg_shading");
   return out;
 }
-Tensor sg_shading_meta(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t, int64_t, int64_t) {
-  const auto d = check_sg(axis, lamb, weight);
-  return at::empty({d.bn, 3, d.R, d.C}, axis.options());
+Tensor sg_shading_meta(const Tensor& axis, const Tensor& lamb, const Tensor& weight, int64_t eh, int64_t ew, int64_t) {
+  const auto d = check_sg_to_env(axis, lamb, weight, eh, ew, false);
+  return rgb(d.bn, d.R, d.C, axis.options());
 }
+void check_light_albedo_scale(const Tensor& dn, const Tensor& d, const Tensor& sn, const Tensor& s, const Tensor& alb, bool device) {
+  require_hip({&dn, &d, &sn, &s, &alb}, device);
+  TORCH_CHECK(dn.sizes() == d.sizes() && dn.sizes() == sn.sizes() && dn.sizes() == s.sizes(), "sgrender: light_albedo_scale needs four render images of one shape");
+}
+Tensor light_albedo_scale_output(const at::TensorOptions& o) { return at::empty({4}, o); }
 Tensor light_albedo_scale_cuda(const Tensor& dn, const Tensor& d, const Tensor& sn, const Tensor& s, const Tensor& alb) {
-  const auto dev = require_hip({&dn, &d, &sn, &s, &alb});
-  const c10::DeviceGuard guard(dev);
+  check_light_albedo_scale(dn, d, sn, s, alb, true);
+  const c10::DeviceGuard guard(dn.device());
+  Tensor out = light_albedo_scale_output(dn.options()), ws = at::empty({api().sgr_glue_workspace_floats(1)}, dn.options());
   const Tensor a = dn.contiguous(), b = d.contiguous(), c = sn.contiguous(), e = s.contiguous(), al = alb.contiguous();
-  TORCH_CHECK(a.sizes() == b.sizes() && a.sizes() == c.sizes() && a.sizes() == e.sizes(), "sgrender: light_albedo_scale needs four render images of one shape");
-  Tensor out = at::empty({4}, a.options()), ws = at::empty({api().sgr_glue_workspace_floats(1)}, a.options());
-  ok(api().sgr_light_albedo_scale(rp(a), rp(b), rp(c), rp(e), rp(al), wp(out), wp(ws), (long long)b.numel(), (long long)al.numel(), stream_of(dev)),
+  ok(api().sgr_light_albedo_scale(rp(a), rp(b), rp(c), rp(e), rp(al), wp(out), wp(ws), (long long)b.numel(), (long long)al.numel(), stream_of(dn.device())),
      "sgr_light_albedo_scale");
   return out;
 }
-Tensor light_albedo_scale_meta(const Tensor& dn, const Tensor&, const Tensor&, const Tensor&, const Tensor&) { return at::empty({4}, dn.options()); }
-T3 light_encoder_input_cuda(const Tensor& im, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& depth, int64_t H, int64_t W) {
-  const auto dev = require_hip({&im, &albedo, &normal, &rough, &depth});
-  const c10::DeviceGuard guard(dev);
-  const Tensor i = im.contiguous(), a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), dp = depth.contiguous();
-  TORCH_CHECK(i.dim() == 4 && i.size(1) == 3, "sgrender: light_encoder_input takes im/albedo/normal [bn,3,h,w] and rough/depth [bn,1,h,w]");
-  const int64_t bn = i.size(0), h = i.size(2), w = i.size(3);
-  TORCH_CHECK(a.sizes() == i.sizes() && n.sizes() == i.sizes() && r.sizes() == at::IntArrayRef({bn, 1, h, w}) && dp.sizes() == r.sizes(),
+Tensor light_albedo_scale_meta(const Tensor& dn, const Tensor& d, const Tensor& sn, const Tensor& s, const Tensor& alb) {
+  check_light_albedo_scale(dn, d, sn, s, alb, false);
+  return light_albedo_scale_output(dn.options());
+}
+BrdfDims check_light_encoder_input(const Tensor& im, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& depth, bool device) {
+  require_hip({&im, &albedo, &normal, &rough, &depth}, device);
+  TORCH_CHECK(im.dim() == 4 && im.size(1) == 3, "sgrender: light_encoder_input takes im/albedo/normal [bn,3,h,w] and rough/depth [bn,1,h,w]");
+  const int64_t bn = im.size(0), h = im.size(2), w = im.size(3);
+  TORCH_CHECK(albedo.sizes() == im.sizes() && normal.sizes() == im.sizes() && rough.sizes() == at::IntArrayRef({bn, 1, h, w}) && depth.sizes() == rough.sizes(),
               "sgrender: light_encoder_input takes im/albedo/normal [bn,3,h,w] and rough/depth [bn,1,h,w]");
-  const auto o = i.options();
-  Tensor out = at::empty({bn, 11, H, W}, o), alb_n = at::empty_like(a), dep_n = at::empty_like(dp), ws = at::empty({api().sgr_glue_workspace_floats((int)bn)}, o);
-  ok(api().sgr_light_input_fwd(rp(i), rp(a), rp(n), rp(r), rp(dp), wp(out), wp(alb_n), wp(dep_n), wp(ws), (int)bn, (int)h, (int)w, (int)H, (int)W, stream_of(dev)),
+  return {bn, h, w};
+}
+T3 light_encoder_input_outputs(const BrdfDims& d, int64_t H, int64_t W, const at::TensorOptions& o) {      // the encoder's input, normalised albedo, normalised depth
+  return {at::empty({d.bn, 11, H, W}, o), at::empty({d.bn, 3, d.h, d.w}, o), at::empty({d.bn, 1, d.h, d.w}, o)};
+}
+T3 light_encoder_input_cuda(const Tensor& im, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& depth, int64_t H, int64_t W) {
+  const auto d = check_light_encoder_input(im, albedo, normal, rough, depth, true);
+  const c10::DeviceGuard guard(im.device());
+  auto [out, alb_n, dep_n] = light_encoder_input_outputs(d, H, W, im.options());
+  Tensor ws = at::empty({api().sgr_glue_workspace_floats((int)d.bn)}, im.options());
+  const Tensor i = im.contiguous(), a = albedo.contiguous(), n = normal.contiguous(), r = rough.contiguous(), dp = depth.contiguous();
+  ok(api().sgr_light_input_fwd(rp(i), rp(a), rp(n), rp(r), rp(dp), wp(out), wp(alb_n), wp(dep_n), wp(ws), (int)d.bn, (int)d.h, (int)d.w, (int)H, (int)W, stream_of(im.device())),
      "sgr_light_input_fwd");
   return {out, alb_n, dep_n};
 }
-T3 light_encoder_input_meta(const Tensor& im, const Tensor& albedo, const Tensor&, const Tensor&, const Tensor& depth, int64_t H, int64_t W) {
-  return {at::empty({im.size(0), 11, H, W}, im.options()), at::empty(albedo.sizes(), albedo.options()), at::empty(depth.sizes(), depth.options())};
+T3 light_encoder_input_meta(const Tensor& im, const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& depth, int64_t H, int64_t W) {
+  return light_encoder_input_outputs(check_light_encoder_input(im, albedo, normal, rough, depth, false), H, W, im.options());
 }
 
 // ==================================================================================================================
@@ -980,7 +1071,8 @@ Tensor attach_grads6_autograd(const Tensor& value, const Tensor& axis, const Ten
 
 struct ObjDims { int64_t bn, K, R, C, h, w, imH, imW; };
 ObjDims check_objective(const Tensor& albedo, const Tensor& normal, const Tensor& rough, const Tensor& axis, const Tensor& lamb, const Tensor& weight,
-                        const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew) {
+                        const Tensor& im, const Tensor& seg, const Tensor& env_gt, const Tensor& env_ind, int64_t eh, int64_t ew, bool device) {
+  require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind}, device);
   const auto d = check_sg(axis, lamb, weight);
   const auto b = check_brdf(albedo, normal, rough);
   TORCH_CHECK(b.bn == d.bn && env_gt.sizes() == at::IntArrayRef({d.bn, 3, d.R, d.C, eh, ew}), "sgrender: envmapsBatch must be [bn,3,", d.R, ",", d.C, ",", eh, ",", ew,
@@ -999,24 +1091,22 @@ ObjDims check_objective(const Tensor& albedo, const Tensor& normal, const Tensor
 #define OBJ_ARGS OBJ_INPUTS, double ren_w, double rec_w, double offset, bool heads, bool handoff
 #define OBJ_PASS OBJ_INPUTS_PASS, ren_w, rec_w, offset, heads, handoff
 
-// What the one-rank objective and stage 1 of the sharded one do before their first launch: contiguous inputs, the argument checks, the
+// What the one-rank objective and stage 1 of the sharded one do before their first launch: the argument checks, contiguous inputs, the
 // temporaries both fill, the two constant tables.  (A constructor, so that the device guard lives as long as the caller's frame.)
 struct ObjectivePrologue {
+  ObjDims d;
   c10::Device dev;
   c10::DeviceGuard guard;
   Tensor a, n, r, ax, la, we, i, sg, gt, ind;
-  ObjDims d;
   at::TensorOptions o;
   int bn, K, R, C;
   Tensor diffuse, spec, im_s, seg_s, rendered, mask, coef, coef_ds, ws, ws_r, dirs, view;
   void* st;
   explicit ObjectivePrologue(OBJ_INPUTS)
-      : dev(require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &im, &seg, &env_gt, &env_ind})), guard(dev), a(albedo.contiguous()),
-        n(normal.contiguous()), r(rough.contiguous()), ax(axis.contiguous()), la(lamb.contiguous()), we(weight.contiguous()), i(im.contiguous()),
-        sg(seg.contiguous()), gt(env_gt.contiguous()), ind(env_ind.contiguous().reshape({-1})), d(check_objective(a, n, r, ax, la, we, i, sg, gt, ind, eh, ew)),
-        o(a.options()), bn((int)d.bn), K((int)d.K), R((int)d.R), C((int)d.C) {
-    auto img = [&] { return at::empty({d.bn, 3, d.R, d.C}, o); };
-    diffuse = img(); spec = img(); im_s = img(); rendered = img();
+      : d(check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, true)), dev(albedo.device()), guard(dev),
+        a(albedo.contiguous()), n(normal.contiguous()), r(rough.contiguous()), ax(axis.contiguous()), la(lamb.contiguous()), we(weight.contiguous()),
+        i(im.contiguous()), sg(seg.contiguous()), gt(env_gt.contiguous()), ind(env_ind.contiguous().reshape({-1})), o(a.options()), bn((int)d.bn), K((int)d.K), R((int)d.R), C((int)d.C) {
+    diffuse = rgb(d.bn, d.R, d.C, o); spec = rgb(d.bn, d.R, d.C, o); im_s = rgb(d.bn, d.R, d.C, o); rendered = rgb(d.bn, d.R, d.C, o);
     seg_s = at::empty({d.bn, 1, d.R, d.C}, o); mask = at::empty({d.bn, d.R * d.C}, o); coef = at::empty({d.bn}, o); coef_ds = at::empty({d.bn, 2}, o);
     ws = at::empty({api().sgr_fused_recon_workspace_floats(bn, R, C)}, o); ws_r = loss_workspace(d.bn, a);
     dirs = dirs_table(dev, eh, ew); view = view_table(dev, d.R, d.C, fov, cam);
@@ -1080,7 +1170,7 @@ T12 objective_fwdbwd(OBJ_ARGS, bool need_grad, MapWants want) {
           want.rough ? g_rgh : Tensor(), applied};
 }
 T12 objective_fwdbwd_shapes(OBJ_ARGS, bool need_grad, MapWants want) {
-  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
+  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, false);
   const auto o = albedo.options();
   auto g = [&](const Tensor& t, bool wanted) { return wanted ? at::empty(t.sizes(), o) : Tensor(); };
   return {at::empty({}, o), at::empty({}, o), at::empty({}, o), at::empty({d.bn, 3, d.R, d.C}, o), at::empty({d.bn}, o), g(axis, need_grad), g(lamb, need_grad),
@@ -1190,7 +1280,7 @@ T12 light_objective_stage1_cuda(OBJ_INPUTS, bool heads, bool handoff) {
   return {p.diffuse, p.spec, p.mask, p.coef, p.im_s, p.seg_s, p.rendered, p.coef_ds, sums, p.ws, lam_t, w_t};
 }
 T12 light_objective_stage1_meta(OBJ_INPUTS, bool heads, bool handoff) {
-  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew);
+  const auto d = check_objective(albedo, normal, rough, axis, lamb, weight, im, seg, env_gt, env_ind, eh, ew, false);
   const auto o = albedo.options();
   const bool h = handoff && !heads;
   auto img = [&] { return at::empty({d.bn, 3, d.R, d.C}, o); };
@@ -1245,7 +1335,7 @@ T8 objective_stage2(STAGE2_ARGS, bool need_grad, MapWants want) {
   return {render_err, g_axis, g_lamb, g_weight, want.albedo ? g_alb : Tensor(), want.normal ? g_nrm : Tensor(), want.rough ? g_rgh : Tensor(), parts_b};
 }
 T8 objective_stage2_shapes(STAGE2_ARGS, bool need_grad, MapWants want) {
-  require_fp32({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws});
+  require_hip({&albedo, &normal, &rough, &axis, &lamb, &weight, &env_gt, &mask, &coef, &diffuse, &spec, &im_s, &seg_s, &coef_ds, &sums, &ws}, false);
   const auto d = check_sg(axis, lamb, weight);
   check_brdf(albedo, normal, rough);
   check_stage1_tensors(d.bn, d.R, d.C, mask, coef, diffuse, spec, im_s, seg_s, coef_ds, sums, ws);
@@ -1266,132 +1356,30 @@ T8 light_objective_stage2_brdf_meta(STAGE2_ARGS, bool want_albedo, bool want_nor
 }
 
 // stage 3 (num_e = the rank-summed reconstruction numerator): the objective's scalar tail
+void check_light_objective_stage3(const Tensor& render_err, const Tensor& num_e, const Tensor& sums, bool device) {
+  require_hip({&render_err, &num_e, &sums}, device);
+  TORCH_CHECK(count(num_e) >= 1 && count(sums) == 4 && sums.is_contiguous(), "sgrender: light_objective_stage3 arguments");
+}
+T2 light_objective_stage3_outputs(const at::TensorOptions& o) { return {at::empty({}, o), at::empty({}, o)}; }      // objective, recon_err
 T2 light_objective_stage3_cuda(const Tensor& render_err, const Tensor& num_e, const Tensor& sums, double ren_w, double rec_w, int64_t eh, int64_t ew) {
-  const auto dev = require_hip({&render_err, &num_e, &sums});
-  const c10::DeviceGuard guard(dev);
-  TORCH_CHECK(num_e.numel() >= 1 && sums.numel() == 4 && sums.is_contiguous(), "sgrender: light_objective_stage3 arguments");
+  check_light_objective_stage3(render_err, num_e, sums, true);
+  const c10::DeviceGuard guard(render_err.device());
   const auto o = render_err.options();
-  Tensor pe = at::empty({2}, o), objective = at::empty({}, o), recon_err = at::empty({}, o);
+  T2 out = light_objective_stage3_outputs(o);
+  Tensor pe = at::empty({2}, o);
   pe.slice(0, 0, 1).copy_(num_e.reshape({-1}).slice(0, 0, 1));
   pe.slice(0, 1, 2).copy_(sums.slice(0, 3, 4));
-  ok(api().sgr_objective_finalize(rp(render_err), rp(pe), (float)ren_w, (float)rec_w, 3.0f * (float)(eh * ew), objective.data_ptr<float>(), recon_err.data_ptr<float>(),
-                                  stream_of(dev)),
+  ok(api().sgr_objective_finalize(rp(render_err), rp(pe), (float)ren_w, (float)rec_w, 3.0f * (float)(eh * ew), std::get<0>(out).data_ptr<float>(),
+                                  std::get<1>(out).data_ptr<float>(), stream_of(render_err.device())),
      "sgr_objective_finalize");
-  return {objective, recon_err};
+  return out;
 }
-T2 light_objective_stage3_meta(const Tensor& render_err, const Tensor&, const Tensor&, double, double, int64_t, int64_t) {
-  return {at::empty({}, render_err.options()), at::empty({}, render_err.options())};
+T2 light_objective_stage3_meta(const Tensor& render_err, const Tensor& num_e, const Tensor& sums, double, double, int64_t, int64_t) {
+  check_light_objective_stage3(render_err, num_e, sums, false);
+  return light_objective_stage3_outputs(render_err.options());
 }
 
 }  // namespace
-
-// ==================================================================================================================
-// in-stream collectives ("optional native variant: ncclAllReduce on the same HIP stream from the extension")
-// ==================================================================================================================
-// The batch-sharded losses couple the ranks through one all-reduce of a handful of floats between two kernels of the step
-// (wrapperBRDFLight.py:192,205-207 under sharding).  Through c10d that is a Python call, ProcessGroupNCCL's bookkeeping and -- at
-// world 1, measured in round 5 -- 9 us per all-reduce on the step.  Here the extension owns an RCCL communicator per process group
-// (bootstrapped once by the host layer: ncclGetUniqueId on rank 0, the 128 bytes broadcast through the existing c10d group) and
-// `allreduce_sum_` enqueues ncclAllReduce on the CURRENT HIP stream: no side stream, no event pair, capturable in a HIP graph.
-// The RCCL used is the one already in the process (PyTorch-ROCm links it): found among the loaded objects, never a second copy.
-struct Rccl {
-  decltype(&::ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&::ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&::ncclAllReduce) AllReduce = nullptr;
-  decltype(&::ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&::ncclGetErrorString) GetErrorString = nullptr;
-  std::string path;
-};
-int find_rccl(struct dl_phdr_info* info, size_t, void* out) {
-  if (info->dlpi_name && std::strstr(info->dlpi_name, "librccl")) {
-    *static_cast<std::string*>(out) = info->dlpi_name;
-    return 1;
-  }
-  return 0;
-}
-const Rccl& rccl() {
-  static const Rccl r = [] {
-    Rccl x;
-    dl_iterate_phdr(&find_rccl, &x.path);
-    TORCH_CHECK(!x.path.empty(), "sgrender: no librccl in this process (PyTorch-ROCm loads it with its distributed backend); the in-stream all-reduce needs it");
-    void* h = dlopen(x.path.c_str(), RTLD_NOW | RTLD_NOLOAD);
-    TORCH_CHECK(h, "sgrender: cannot re-open ", x.path, ": ", dlerror());
-#define SGR_RCCL(name)                                                                \
-  x.name = reinterpret_cast<decltype(x.name)>(dlsym(h, "nccl" #name));                \
-  TORCH_CHECK(x.name, "sgrender: ", x.path, " does not export nccl" #name);
-    SGR_RCCL(GetUniqueId) SGR_RCCL(CommInitRank) SGR_RCCL(AllReduce) SGR_RCCL(CommDestroy) SGR_RCCL(GetErrorString)
-#undef SGR_RCCL
-    return x;
-  }();
-  return r;
-}
-void rccl_ok(ncclResult_t rc, const char* what) { TORCH_CHECK(rc == ncclSuccess, "sgrender: ", what, " failed: ", rccl().GetErrorString(rc)); }
-
-struct CommEntry { ncclComm_t comm; int device, rank, world; };
-std::mutex g_comm_mutex;
-std::map<int64_t, CommEntry> g_comms;
-int64_t g_next_comm = 1;
-
-Tensor comm_unique_id() {
-  static_assert(sizeof(ncclUniqueId) == NCCL_UNIQUE_ID_BYTES, "ncclUniqueId is an opaque byte array");
-  ncclUniqueId id;
-  rccl_ok(rccl().GetUniqueId(&id), "ncclGetUniqueId");
-  Tensor t = at::empty({(int64_t)sizeof(id)}, at::TensorOptions().dtype(at::kByte));
-  std::memcpy(t.data_ptr<uint8_t>(), &id, sizeof(id));
-  return t;
-}
-// collective over the ranks of the communicator being made (ncclCommInitRank synchronises with them); device = this rank's GPU
-int64_t comm_init(const Tensor& uid, int64_t rank, int64_t world, int64_t device) {
-  TORCH_CHECK(uid.device().is_cpu() && uid.scalar_type() == at::kByte && uid.is_contiguous() && uid.numel() == (int64_t)sizeof(ncclUniqueId),
-              "sgrender: comm_init needs the ", sizeof(ncclUniqueId), " bytes of comm_unique_id() as a CPU uint8 tensor");
-  TORCH_CHECK(world >= 1 && rank >= 0 && rank < world, "sgrender: comm_init: rank ", rank, " of ", world);
-  ncclUniqueId id;
-  std::memcpy(&id, uid.const_data_ptr<uint8_t>(), sizeof(id));
-  const c10::DeviceGuard guard(c10::Device(c10::kCUDA, (c10::DeviceIndex)device));
-  ncclComm_t comm = nullptr;
-  rccl_ok(rccl().CommInitRank(&comm, (int)world, id, (int)rank), "ncclCommInitRank");
-  std::lock_guard<std::mutex> lock(g_comm_mutex);
-  const int64_t h = g_next_comm++;
-  g_comms[h] = CommEntry{comm, (int)device, (int)rank, (int)world};
-  return h;
-}
-void comm_destroy(int64_t handle) {
-  CommEntry e{};
-  {
-    std::lock_guard<std::mutex> lock(g_comm_mutex);
-    auto it = g_comms.find(handle);
-    if (it == g_comms.end()) return;
-    e = it->second;
-    g_comms.erase(it);
-  }
-  const c10::DeviceGuard guard(c10::Device(c10::kCUDA, (c10::DeviceIndex)e.device));
-  rccl_ok(rccl().CommDestroy(e.comm), "ncclCommDestroy");
-}
-int64_t comm_world_size(int64_t handle) {
-  std::lock_guard<std::mutex> lock(g_comm_mutex);
-  auto it = g_comms.find(handle);
-  TORCH_CHECK(it != g_comms.end(), "sgrender: unknown communicator handle ", handle);
-  return it->second.world;
-}
-// t <- sum over the ranks of t, enqueued on the current stream of t's device (fp32 / fp64, contiguous)
-void allreduce_sum_cuda(Tensor& t, int64_t handle) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "sgrender: allreduce_sum_ needs a contiguous device tensor");
-  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble, "sgrender: allreduce_sum_ needs fp32 or fp64, got ", t.scalar_type());
-  CommEntry e{};
-  {
-    std::lock_guard<std::mutex> lock(g_comm_mutex);
-    auto it = g_comms.find(handle);
-    TORCH_CHECK(it != g_comms.end(), "sgrender: unknown communicator handle ", handle);
-    e = it->second;
-  }
-  TORCH_CHECK(t.device().index() == e.device, "sgrender: allreduce_sum_: the tensor lives on device ", (int)t.device().index(), ", the communicator on ", e.device);
-  if (t.numel() == 0) return;
-  const c10::DeviceGuard guard(t.device());
-  rccl_ok(rccl().AllReduce(t.data_ptr(), t.data_ptr(), (size_t)t.numel(), t.scalar_type() == at::kFloat ? ncclFloat32 : ncclFloat64, ncclSum, e.comm,
-                           (hipStream_t)stream_of(t.device())),
-          "ncclAllReduce");
-}
-void allreduce_sum_meta(Tensor&, int64_t) {}
 
 TORCH_LIBRARY(sgrender, m) {
   m.def("sg_to_env(Tensor axis, Tensor lamb, Tensor weight, int eh, int ew, bool premap, bool want_tan=False) -> (Tensor, Tensor, Tensor)");
@@ -1449,12 +1437,6 @@ TORCH_LIBRARY(sgrender, m) {
   m.def("table_cache_count(int kind) -> int", &table_cache_count);
   m.def("cached_tables() -> Tensor[]", &cached_tables);
   m.def("recon_workspace_floats(int bn, int R, int C) -> int", &recon_workspace_floats);
-  // in-stream collectives: communicator management is host-side (no dispatch key); the all-reduce itself is a device operator
-  m.def("comm_unique_id() -> Tensor", &comm_unique_id);
-  m.def("comm_init(Tensor uid, int rank, int world, int device) -> int", &comm_init);
-  m.def("comm_destroy(int comm) -> ()", &comm_destroy);
-  m.def("comm_world_size(int comm) -> int", &comm_world_size);
-  m.def("allreduce_sum_(Tensor(a!) t, int comm) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sgrender, CUDA, m) {
@@ -1489,44 +1471,40 @@ TORCH_LIBRARY_IMPL(sgrender, CUDA, m) {
   m.impl("light_objective_brdf_fwdbwd", &light_objective_brdf_fwdbwd_cuda);
   m.impl("light_objective_brdf", &light_objective_backend);
   m.impl("light_objective_stage2_brdf", &light_objective_stage2_brdf_cuda);
-  m.impl("allreduce_sum_", &allreduce_sum_cuda);
 }
 
 TORCH_LIBRARY_IMPL(sgrender, Meta, m) {
-  // fp32_only: the dtype refusal of the device kernels' require_hip, so that a fake-tensor run raises where the device would
-
-  m.impl("sg_to_env", &fp32_only<&sg_to_env_meta>::call);
-  m.impl("sg_to_env_bwd", &fp32_only<&sg_to_env_bwd_meta>::call);
-  m.impl("render_env", &fp32_only<&render_env_meta>::call);
-  m.impl("render_env_bwd_env", &fp32_only<&render_env_bwd_env_meta>::call);
-  m.impl("render_bwd_brdf", &fp32_only<&render_bwd_brdf_meta>::call);
-  m.impl("fused_render", &fp32_only<&fused_render_meta>::call);
-  m.impl("fused_render_bwd_sg", &fp32_only<&fused_render_bwd_sg_meta>::call);
-  m.impl("lsregress_coef", &fp32_only<&lsregress_coef_meta>::call);
-  m.impl("lsregress_diffspec_coef", &fp32_only<&lsregress_diffspec_coef_meta>::call);
-  m.impl("render_loss", &fp32_only<&render_loss_meta>::call);
-  m.impl("render_loss_bwd", &fp32_only<&render_loss_bwd_meta>::call);
-  m.impl("render_loss_finalize", &fp32_only<&render_loss_finalize_meta>::call);
-  m.impl("recon_loss_parts", &fp32_only<&recon_loss_parts_meta>::call);
-  m.impl("recon_loss_bwd", &fp32_only<&recon_loss_bwd_meta>::call);
-  m.impl("light_heads", &fp32_only<&light_heads_meta>::call);
-  m.impl("light_heads_bwd", &fp32_only<&light_heads_bwd_meta>::call);
-  m.impl("sg_shading", &fp32_only<&sg_shading_meta>::call);
-  m.impl("light_albedo_scale", &fp32_only<&light_albedo_scale_meta>::call);
-  m.impl("light_encoder_input", &fp32_only<&light_encoder_input_meta>::call);
+  m.impl("sg_to_env", &sg_to_env_meta);
+  m.impl("sg_to_env_bwd", &sg_to_env_bwd_meta);
+  m.impl("render_env", &render_env_meta);
+  m.impl("render_env_bwd_env", &render_env_bwd_env_meta);
+  m.impl("render_bwd_brdf", &render_bwd_brdf_meta);
+  m.impl("fused_render", &fused_render_meta);
+  m.impl("fused_render_bwd_sg", &fused_render_bwd_sg_meta);
+  m.impl("lsregress_coef", &lsregress_coef_meta);
+  m.impl("lsregress_diffspec_coef", &lsregress_diffspec_coef_meta);
+  m.impl("render_loss", &render_loss_meta);
+  m.impl("render_loss_bwd", &render_loss_bwd_meta);
+  m.impl("render_loss_finalize", &render_loss_finalize_meta);
+  m.impl("recon_loss_parts", &recon_loss_parts_meta);
+  m.impl("recon_loss_bwd", &recon_loss_bwd_meta);
+  m.impl("light_heads", &light_heads_meta);
+  m.impl("light_heads_bwd", &light_heads_bwd_meta);
+  m.impl("sg_shading", &sg_shading_meta);
+  m.impl("light_albedo_scale", &light_albedo_scale_meta);
+  m.impl("light_encoder_input", &light_encoder_input_meta);
   m.impl("rescale_grads_", &rescale_grads_meta);
   m.impl("attach_grads", &attach_grads_backend);
-  m.impl("light_objective_fwdbwd", &fp32_only<&light_objective_fwdbwd_meta>::call);
+  m.impl("light_objective_fwdbwd", &light_objective_fwdbwd_meta);
   m.impl("light_objective", &light_objective_backend);
-  m.impl("light_objective_stage1", &fp32_only<&light_objective_stage1_meta>::call);
+  m.impl("light_objective_stage1", &light_objective_stage1_meta);
   m.impl("light_objective_stage2", &light_objective_stage2_meta);
-  m.impl("light_objective_stage3", &fp32_only<&light_objective_stage3_meta>::call);
+  m.impl("light_objective_stage3", &light_objective_stage3_meta);
   m.impl("rescale_grads6_", &rescale_grads6_meta);
   m.impl("attach_grads6", &attach_grads6_backend);
-  m.impl("light_objective_brdf_fwdbwd", &fp32_only<&light_objective_brdf_fwdbwd_meta>::call);
+  m.impl("light_objective_brdf_fwdbwd", &light_objective_brdf_fwdbwd_meta);
   m.impl("light_objective_brdf", &light_objective_backend);
   m.impl("light_objective_stage2_brdf", &light_objective_stage2_brdf_meta);
-  m.impl("allreduce_sum_", &allreduce_sum_meta);
 }
 
 TORCH_LIBRARY_IMPL(sgrender, Autograd, m) {
@@ -1547,6 +1525,6 @@ TORCH_LIBRARY_IMPL(sgrender, CPU, m) {
   register_no_cpu(m, {"sg_to_env", "sg_to_env_bwd", "render_env", "render_env_bwd_env", "render_bwd_brdf", "fused_render", "fused_render_bwd_sg", "lsregress_coef",
                       "lsregress_diffspec_coef", "render_loss", "render_loss_bwd", "render_loss_finalize", "recon_loss_parts", "recon_loss_bwd", "light_heads",
                       "light_heads_bwd", "sg_shading", "light_albedo_scale", "light_encoder_input", "rescale_grads_", "attach_grads", "light_objective_fwdbwd",
-                      "light_objective", "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "allreduce_sum_", "rescale_grads6_",
+                      "light_objective", "light_objective_stage1", "light_objective_stage2", "light_objective_stage3", "rescale_grads6_",
                       "attach_grads6", "light_objective_brdf_fwdbwd", "light_objective_brdf", "light_objective_stage2_brdf"});
 }

@@ -87,47 +87,57 @@ T7 bilateral_grid_meta(const Tensor& image, double, double, double) {
 #define GRID_PTRS pix2vert.const_data_ptr<int>(), perm.const_data_ptr<int>(), seg.const_data_ptr<int>(), nbr.const_data_ptr<int>(), nvert.const_data_ptr<int>(), \
                   m.const_data_ptr<double>(), n.const_data_ptr<double>()
 
-T2 bilateral_solve_fwd_cuda(GRID_ARGS, const Tensor& pred, const Tensor& conf, double lam, double amin, double tol, int64_t maxiter) {
-  TORCH_CHECK(pred.is_cuda(), kNoCpu);
-  const auto dev = pred.device();
-  require_dev({&pix2vert, &perm, &seg, &nbr, &nvert, &m, &n, &conf}, dev);
-  const c10::DeviceGuard guard(dev);
+// shared by the device and the Meta kernels: a traced graph cannot pass tracing and then fail on the device
+Dims check_solve_fwd(GRID_ARGS, const Tensor& pred, const Tensor& conf, bool device) {
+  if (device) {
+    TORCH_CHECK(pred.is_cuda(), kNoCpu);
+    require_dev({&pix2vert, &perm, &seg, &nbr, &nvert, &m, &n, &conf}, pred.device());
+  }
   check_grid(pix2vert, perm, seg, nbr, nvert, m, n);
-  const auto d = check_target(pred, conf, pix2vert);
+  return check_target(pred, conf, pix2vert);
+}
+T2 solve_fwd_outputs(const Dims& d, const at::TensorOptions& o) { return {at::empty({d.B, d.C, d.H, d.W}, o), at::empty({d.B, d.H * d.W, d.C}, o.dtype(at::kDouble))}; }
+T2 bilateral_solve_fwd_cuda(GRID_ARGS, const Tensor& pred, const Tensor& conf, double lam, double amin, double tol, int64_t maxiter) {
+  const auto d = check_solve_fwd(pix2vert, perm, seg, nbr, nvert, m, n, pred, conf, true);
+  const c10::DeviceGuard guard(pred.device());
+  auto [out, yhat] = solve_fwd_outputs(d, pred.options());
   const Tensor t = pred.contiguous(), w = conf.contiguous();
-  Tensor out = at::empty({d.B, d.C, d.H, d.W}, t.options()), yhat = at::empty({d.B, d.H * d.W, d.C}, t.options().dtype(at::kDouble));
   Tensor ws = workspace(d.B, d.H, d.W, d.C, t.options());
   ok(api().sgr_bs_solve_fwd(GRID_PTRS, t.const_data_ptr<float>(), w.const_data_ptr<float>(), out.data_ptr<float>(), yhat.data_ptr<double>(), ws.data_ptr(), (int)d.B,
-                            (int)d.C, (int)d.H, (int)d.W, lam, amin, tol, (int)maxiter, stream_of(dev)),
+                            (int)d.C, (int)d.H, (int)d.W, lam, amin, tol, (int)maxiter, stream_of(pred.device())),
      "sgr_bs_solve_fwd");
   return {out, yhat};
 }
 T2 bilateral_solve_fwd_meta(GRID_ARGS, const Tensor& pred, const Tensor& conf, double, double, double, int64_t) {
-  const auto d = check_target(pred, conf, pix2vert);
-  return {at::empty({d.B, d.C, d.H, d.W}, pred.options()), at::empty({d.B, d.H * d.W, d.C}, pred.options().dtype(at::kDouble))};
+  return solve_fwd_outputs(check_solve_fwd(pix2vert, perm, seg, nbr, nvert, m, n, pred, conf, false), pred.options());
 }
 
-T2 bilateral_solve_bwd_cuda(GRID_ARGS, const Tensor& g_out, const Tensor& pred, const Tensor& conf, const Tensor& yhat, double lam, double amin, double tol,
-                            int64_t maxiter) {
-  TORCH_CHECK(pred.is_cuda(), kNoCpu);
-  const auto dev = pred.device();
-  require_dev({&pix2vert, &perm, &seg, &nbr, &nvert, &m, &n, &conf, &g_out, &yhat}, dev);
-  const c10::DeviceGuard guard(dev);
+Dims check_solve_bwd(GRID_ARGS, const Tensor& g_out, const Tensor& pred, const Tensor& conf, const Tensor& yhat, bool device) {
+  if (device) {
+    TORCH_CHECK(pred.is_cuda(), kNoCpu);
+    require_dev({&pix2vert, &perm, &seg, &nbr, &nvert, &m, &n, &conf, &g_out, &yhat}, pred.device());
+  }
   check_grid(pix2vert, perm, seg, nbr, nvert, m, n);
   const auto d = check_target(pred, conf, pix2vert);
   TORCH_CHECK(g_out.sizes() == pred.sizes() && g_out.scalar_type() == at::kFloat, "sgrender: the bilateral cotangent must match the target: ", g_out.sizes());
   TORCH_CHECK(yhat.sizes() == at::IntArrayRef({d.B, d.H * d.W, d.C}) && yhat.scalar_type() == at::kDouble, "sgrender: yhat must be the fp64 [B,H*W,C] tensor of the forward solve");
+  return d;
+}
+T2 solve_bwd_outputs(const Dims& d, const at::TensorOptions& o) { return {at::empty({d.B, d.C, d.H, d.W}, o), at::empty({d.B, 1, d.H, d.W}, o)}; }      // g_pred, g_conf
+T2 bilateral_solve_bwd_cuda(GRID_ARGS, const Tensor& g_out, const Tensor& pred, const Tensor& conf, const Tensor& yhat, double lam, double amin, double tol,
+                            int64_t maxiter) {
+  const auto d = check_solve_bwd(pix2vert, perm, seg, nbr, nvert, m, n, g_out, pred, conf, yhat, true);
+  const c10::DeviceGuard guard(pred.device());
+  auto [gp, gc] = solve_bwd_outputs(d, pred.options());
   const Tensor g = g_out.contiguous(), t = pred.contiguous(), w = conf.contiguous(), yh = yhat.contiguous();
-  Tensor gp = at::empty_like(t), gc = at::empty_like(w);
   Tensor ws = workspace(d.B, d.H, d.W, d.C, t.options());
   ok(api().sgr_bs_solve_bwd(GRID_PTRS, g.const_data_ptr<float>(), t.const_data_ptr<float>(), w.const_data_ptr<float>(), yh.const_data_ptr<double>(), gp.data_ptr<float>(),
-                            gc.data_ptr<float>(), ws.data_ptr(), (int)d.B, (int)d.C, (int)d.H, (int)d.W, lam, amin, tol, (int)maxiter, stream_of(dev)),
+                            gc.data_ptr<float>(), ws.data_ptr(), (int)d.B, (int)d.C, (int)d.H, (int)d.W, lam, amin, tol, (int)maxiter, stream_of(pred.device())),
      "sgr_bs_solve_bwd");
   return {gp, gc};
 }
-T2 bilateral_solve_bwd_meta(GRID_ARGS, const Tensor& g_out, const Tensor& pred, const Tensor& conf, const Tensor&, double, double, double, int64_t) {
-  check_target(pred, conf, pix2vert);
-  return {at::empty(pred.sizes(), pred.options()), at::empty(conf.sizes(), conf.options())};
+T2 bilateral_solve_bwd_meta(GRID_ARGS, const Tensor& g_out, const Tensor& pred, const Tensor& conf, const Tensor& yhat, double, double, double, int64_t) {
+  return solve_bwd_outputs(check_solve_bwd(pix2vert, perm, seg, nbr, nvert, m, n, g_out, pred, conf, yhat, false), pred.options());
 }
 
 using GridSig = T7(const Tensor&, double, double, double);

@@ -17,8 +17,6 @@ using namespace sgr_host;
 using OT = OptTensor;
 using W4 = at::ArrayRef<double>;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 // ---- the objective: argument checks shared by the device and the Meta kernels -----------------------------------------------------------
 struct Planes {
   Tensor aP, aG, nP, nG, rP, rG, dP, dG, sB, sA, sD;      // contiguous copies (undefined = absent)
@@ -204,12 +202,11 @@ struct BrdfObjectiveFn : public torch::autograd::Function<BrdfObjectiveFn> {
     for (int k = 0; k < 5; ++k) any = any || g[k].defined();
     if (!any) return out;
     const auto s = ctx->get_saved_variables();
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     const auto w = ctx->saved_data["w"].toDoubleVector();
     const bool need[4] = {ctx->saved_data["nA"].toBool(), ctx->saved_data["nN"].toBool(), ctx->saved_data["nR"].toBool(), ctx->saved_data["nD"].toBool()};
     static auto bwd = find_op<BwdSig>("sgrender::brdf_objective_bwd");
-    auto [gA, gN, gR, gD] = bwd.call(opt(g[0]), opt(g[1]), opt(g[2]), opt(g[3]), opt(g[4]), opt(s[0]), opt(s[1]), opt(s[2]), opt(s[3]), opt(s[4]), opt(s[5]), opt(s[6]),
-                                     opt(s[7]), opt(s[8]), opt(s[9]), opt(s[10]), s[11], s[12], w, ctx->saved_data["off"].toDouble(), need[0], need[1], need[2], need[3]);
+    auto [gA, gN, gR, gD] = bwd.call(opt_of(g[0]), opt_of(g[1]), opt_of(g[2]), opt_of(g[3]), opt_of(g[4]), opt_of(s[0]), opt_of(s[1]), opt_of(s[2]), opt_of(s[3]), opt_of(s[4]), opt_of(s[5]), opt_of(s[6]),
+                                     opt_of(s[7]), opt_of(s[8]), opt_of(s[9]), opt_of(s[10]), s[11], s[12], w, ctx->saved_data["off"].toDouble(), need[0], need[1], need[2], need[3]);
     if (need[0]) out[0] = gA;
     if (need[1]) out[2] = gN;
     if (need[2]) out[4] = gR;

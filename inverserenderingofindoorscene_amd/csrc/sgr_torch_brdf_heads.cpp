@@ -11,8 +11,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 #define HEAD_ARGS const OT &x_albedo, const OT &x_normal, const OT &x_rough, const OT &x_depth
 #define HEAD_PASS x_albedo, x_normal, x_rough, x_depth
 #define HEAD_SCHEMA "Tensor? x_albedo, Tensor? x_normal, Tensor? x_rough, Tensor? x_depth"
@@ -142,7 +140,6 @@ struct BrdfHeadsFn : public torch::autograd::Function<BrdfHeadsFn> {
   static variable_list backward(AutogradContext* ctx, variable_list g) {
     variable_list out(9);
     const auto s = ctx->get_saved_variables();
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     bool need[4], any = false;
     for (int k = 0; k < 4; ++k) {
       need[k] = s[k].defined();
@@ -152,7 +149,7 @@ struct BrdfHeadsFn : public torch::autograd::Function<BrdfHeadsFn> {
     static auto bwd = find_op<BwdSig>("sgrender::brdf_heads_bwd");
     // an output nobody used arrives undefined and travels on as None: a zero cotangent through a NULL pointer
     auto cot = [&](int k) { return need[k] && g[k].defined() ? OT(g[k]) : OT(); };
-    auto [gA, gN, gR, gD] = bwd.call(opt(s[0]), opt(s[1]), opt(s[2]), opt(s[3]), cot(0), cot(1), cot(2), cot(3), ctx->saved_data["unit"].toBool(), need[0], need[1], need[2],
+    auto [gA, gN, gR, gD] = bwd.call(opt_of(s[0]), opt_of(s[1]), opt_of(s[2]), opt_of(s[3]), cot(0), cot(1), cot(2), cot(3), ctx->saved_data["unit"].toBool(), need[0], need[1], need[2],
                                      need[3]);
     if (need[0]) out[0] = gA;
     if (need[1]) out[1] = gN;

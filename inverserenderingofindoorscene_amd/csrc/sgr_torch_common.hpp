@@ -1,4 +1,4 @@
-// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
+// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp, sgr_torch_comm.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
 // resolved ONCE for the whole extension, and the few helpers every operator file needs around it.
 //
 // The C ABI stays the drop-in boundary: resolved with dlopen at first use ($SGR_LIB, else the libsgrender.so next to the extension's
@@ -113,6 +113,22 @@ inline const float* rp(const Tensor* t) { return t ? rp(*t) : nullptr; }
 inline float* wp(const Tensor& t) { return t.defined() && t.numel() ? t.data_ptr<float>() : nullptr; }
 
 inline void* stream_of(const c10::Device& dev) { return c10::hip::getCurrentHIPStream(dev.index()).stream(); }
+
+// "given" for a tensor (defined and not empty) and for an optional one; an undefined saved tensor or cotangent as nullopt (autograd nodes)
+inline bool present(const Tensor& t) { return t.defined() && t.numel() > 0; }
+inline bool has(const OptTensor& t) { return t.has_value() && t->defined(); }
+inline OptTensor opt_of(const Tensor& t) { return t.defined() ? OptTensor(t) : OptTensor(); }
+// operators return tensors only: a [0] tensor where nothing is wanted
+inline Tensor none(const at::TensorOptions& o) { return at::empty({0}, o); }
+inline Tensor none_like(const Tensor& t) { return none(t.options()); }
+// a 4-D map travels with its strides (channels-last maps and slices are not copied)
+struct Strides4 { long long v[4]; };
+inline Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
+// a workspace of the n floats the C ABI asked for (n <= 0: it has no answer for these sizes)
+inline Tensor workspace_floats(long long n, const char* who, const at::TensorOptions& o) {
+  TORCH_CHECK(n > 0, "sgrender: ", who, ": no workspace size for these sizes");
+  return at::empty({(int64_t)n}, o);
+}
 
 template <typename Sig>
 auto find_op(const char* name) {

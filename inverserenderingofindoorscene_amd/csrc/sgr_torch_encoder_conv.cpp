@@ -12,8 +12,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 constexpr int64_t kMaxC = 160, kMinO = 16, kMaxO = 128;      // kEcMaxC, kEcMinO, kEcMaxO of csrc/sgr_encoder_conv.h
 constexpr const char* kCompose = "; compose F.pad(x, (1, 1, 1, 1), mode=...) and F.conv2d(., stride=2) instead";
 
@@ -46,9 +44,6 @@ Conv check_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias, int64_
   TORCH_CHECK(weight.device() == x.device() && bias.device() == x.device(), "sgrender: encoder_conv: tensors on different devices");
   return s;
 }
-
-struct Strides4 { long long v[4]; };
-Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
 
 Tensor encoder_conv_cuda(const Tensor& x, const Tensor& weight, const Tensor& bias, int64_t pad_mode) {
   const Conv s = check_fwd(x, weight, bias, pad_mode, true);
@@ -93,8 +88,7 @@ Conv check_bwd(const Tensor& g, const OT& x, const OT& weight, int64_t H, int64_
 }
 // a [0] tensor where a gradient is not wanted
 T3 bwd_outputs(const Conv& s, const at::TensorOptions& o, bool nX, bool nW, bool nB) {
-  auto none = [&] { return at::empty({0}, o); };
-  return {nX ? at::empty({s.B, s.C, s.H, s.W}, o) : none(), nW ? at::empty({s.O, s.C, 4, 4}, o) : none(), nB ? at::empty({s.O}, o) : none()};
+  return {nX ? at::empty({s.B, s.C, s.H, s.W}, o) : none(o), nW ? at::empty({s.O, s.C, 4, 4}, o) : none(o), nB ? at::empty({s.O}, o) : none(o)};
 }
 T3 encoder_conv_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, int64_t H, int64_t W, int64_t pad_mode, bool nX, bool nW, bool nB) {
   const Conv s = check_bwd(g, x, weight, H, W, pad_mode, nX, nW, nB, true);
@@ -107,9 +101,7 @@ T3 encoder_conv_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, int64_t
   if (nX) w = weight->contiguous();
   if (nW) xs = strides_of(*x);
   if (nW || nB) {
-    const long long n = api().sgr_encoder_conv_workspace_floats((int)s.B, (int)s.C, (int)s.O, (int)s.H, (int)s.W);
-    TORCH_CHECK(n > 0, "sgrender: encoder_conv_bwd: no workspace size for these sizes");
-    ws = at::empty({(int64_t)n}, o);
+    ws = workspace_floats(api().sgr_encoder_conv_workspace_floats((int)s.B, (int)s.C, (int)s.O, (int)s.H, (int)s.W), "encoder_conv_bwd", o);
   }
   ok(api().sgr_encoder_conv_bwd(rp(gc), nW ? rp(*x) : nullptr, rp(w), wp(std::get<0>(out)), wp(std::get<1>(out)), wp(std::get<2>(out)), wp(ws), (int)s.B, (int)s.C,
                                 (int)s.O, (int)s.H, (int)s.W, nW ? xs.v : nullptr, (int)pad_mode, stream_of(g.device())),
@@ -143,9 +135,8 @@ struct EncoderConvFn : public torch::autograd::Function<EncoderConvFn> {
     if (!g[0].defined()) return out;
     const auto s = ctx->get_saved_variables();
     const bool nX = ctx->saved_data["nX"].toBool(), nW = ctx->saved_data["nW"].toBool(), nB = ctx->saved_data["nB"].toBool();
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     static auto bwd = find_op<BwdSig>("sgrender::encoder_conv_bwd");
-    auto [dx, dw, db] = bwd.call(g[0], opt(s[0]), opt(s[1]), ctx->saved_data["H"].toInt(), ctx->saved_data["W"].toInt(), ctx->saved_data["pad_mode"].toInt(), nX, nW, nB);
+    auto [dx, dw, db] = bwd.call(g[0], opt_of(s[0]), opt_of(s[1]), ctx->saved_data["H"].toInt(), ctx->saved_data["W"].toInt(), ctx->saved_data["pad_mode"].toInt(), nX, nW, nB);
     if (nX) out[0] = dx;
     if (nW) out[1] = dw;
     if (nB) out[2] = db;

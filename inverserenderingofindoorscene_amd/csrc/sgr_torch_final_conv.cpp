@@ -12,8 +12,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 constexpr int64_t kMaxC = 256;      // kFcMaxC of csrc/sgr_final_conv.h: the weight tile stays in LDS
 constexpr const char* kCompose = "; compose F.pad(., (1, 1, 1, 1), mode='replicate') and F.conv2d (after group_norm_relu, if there is a GroupNorm) instead";
 
@@ -55,9 +53,6 @@ Conv check_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias, const 
   return s;
 }
 
-struct Strides4 { long long v[4]; };
-Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
-
 // -> (out [B,3,H,W], stats [B,G,4]; [0] without a GroupNorm)
 T2 final_conv_cuda(const Tensor& x, const Tensor& weight, const Tensor& bias, const OT& gnw, const OT& gnb, int64_t G, double eps) {
   const Conv s = check_fwd(x, weight, bias, gnw, gnb, G, eps, true);
@@ -69,9 +64,7 @@ T2 final_conv_cuda(const Tensor& x, const Tensor& weight, const Tensor& bias, co
   if (s.fused) {
     gw = gnw->contiguous(); gb = gnb->contiguous();
     stats = at::empty({s.B, s.G, 4}, o);
-    const long long n = api().sgr_gn_stage_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, 0, 0);
-    TORCH_CHECK(n > 0, "sgrender: final_conv: no workspace size for these sizes");
-    const Tensor ws = at::empty({(int64_t)n}, o);
+    const Tensor ws = workspace_floats(api().sgr_gn_stage_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, 0, 0), "final_conv", o);
     ok(api().sgr_gn_moments(rp(x), wp(stats), wp(ws), (int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, xs.v, (float)eps, stream_of(x.device())), "sgr_gn_moments");
   }
   ok(api().sgr_final_conv_fwd(rp(x), rp(w), rp(b), rp(gw), rp(gb), s.fused ? rp(stats) : nullptr, wp(out), (int)s.B, (int)s.C, 3, (int)s.G, (int)s.H, (int)s.W, xs.v,
@@ -119,8 +112,7 @@ Conv check_bwd(const Tensor& g, const OT& x, const OT& weight, const OT& gnw, co
 }
 // a [0] tensor where a gradient is not wanted
 T3 bwd_outputs(const Conv& s, const at::TensorOptions& o, bool nY, bool nW, bool nB) {
-  auto none = [&] { return at::empty({0}, o); };
-  return {nY ? at::empty({s.B, s.C, s.H, s.W}, o) : none(), nW ? at::empty({3, s.C, 3, 3}, o) : none(), nB ? at::empty({3}, o) : none()};
+  return {nY ? at::empty({s.B, s.C, s.H, s.W}, o) : none(o), nW ? at::empty({3, s.C, 3, 3}, o) : none(o), nB ? at::empty({3}, o) : none(o)};
 }
 T3 final_conv_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, const OT& gnw, const OT& gnb, const OT& stats, int64_t C, int64_t G, bool nY, bool nW, bool nB) {
   const Conv s = check_bwd(g, x, weight, gnw, gnb, stats, C, G, nY, nW, nB, true);
@@ -136,9 +128,7 @@ T3 final_conv_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, const OT&
     if (s.fused) { gw = gnw->contiguous(); gb = gnb->contiguous(); st = stats->contiguous(); }
   }
   if (nW || nB) {
-    const long long n = api().sgr_final_conv_workspace_floats((int)s.B, (int)s.C, 3, (int)s.H, (int)s.W);
-    TORCH_CHECK(n > 0, "sgrender: final_conv_bwd: no workspace size for these sizes");
-    ws = at::empty({(int64_t)n}, o);
+    ws = workspace_floats(api().sgr_final_conv_workspace_floats((int)s.B, (int)s.C, 3, (int)s.H, (int)s.W), "final_conv_bwd", o);
   }
   ok(api().sgr_final_conv_bwd(rp(gc), nW ? rp(*x) : nullptr, rp(w), rp(gw), rp(gb), rp(st), wp(std::get<0>(out)), wp(std::get<1>(out)), wp(std::get<2>(out)), wp(ws),
                               (int)s.B, (int)s.C, 3, (int)s.G, (int)s.H, (int)s.W, nW ? xs.v : nullptr, stream_of(g.device())),
@@ -183,9 +173,8 @@ struct FinalConvFn : public torch::autograd::Function<FinalConvFn> {
                nGW = ctx->saved_data["nGW"].toBool(), nGB = ctx->saved_data["nGB"].toBool();
     const bool gn_side = fused && (nX || nGW || nGB), need_y = fused ? gn_side : nX;
     const int64_t C = ctx->saved_data["C"].toInt(), G = ctx->saved_data["G"].toInt();
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     static auto bwd = find_op<BwdSig>("sgrender::final_conv_bwd");
-    auto [dy, dw, db] = bwd.call(g[0], nW ? opt(s[0]) : OT(), opt(s[1]), opt(s[2]), opt(s[3]), opt(s[4]), C, G, need_y, nW, nB);
+    auto [dy, dw, db] = bwd.call(g[0], nW ? opt_of(s[0]) : OT(), opt_of(s[1]), opt_of(s[2]), opt_of(s[3]), opt_of(s[4]), C, G, need_y, nW, nB);
     if (nW) out[1] = dw;
     if (nB) out[2] = db;
     if (!fused) {
@@ -194,7 +183,7 @@ struct FinalConvFn : public torch::autograd::Function<FinalConvFn> {
     }
     if (gn_side) {      // the stage's own backward: it recomputes the ReLU's mask from x, so dy goes in unmasked
       static auto gn_bwd = find_op<GnBwdSig>("sgrender::gn_stage_bwd");
-      auto [dx, dgw, dgb, ds] = gn_bwd.call(dy, opt(s[0]), opt(s[2]), opt(s[3]), opt(s[4]), C, (int64_t)0, G, nX, nGW, nGB, false);
+      auto [dx, dgw, dgb, ds] = gn_bwd.call(dy, opt_of(s[0]), opt_of(s[2]), opt_of(s[3]), opt_of(s[4]), C, (int64_t)0, G, nX, nGW, nGB, false);
       if (nX) out[0] = dx;
       if (nGW) out[3] = dgw;
       if (nGB) out[4] = dgb;

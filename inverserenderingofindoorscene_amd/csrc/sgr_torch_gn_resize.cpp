@@ -12,8 +12,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 struct Resize {
   int64_t B = 0, C = 0, Cs = 0, H = 0, W = 0, Hs = 0, Ws = 0, G = 0;
   bool up() const { return Cs > 0; }
@@ -58,13 +56,8 @@ Resize check_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias, cons
   return s;
 }
 
-struct Strides4 { long long v[4]; };
-Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
-
 Tensor workspace(const Resize& s, bool backward, const at::TensorOptions& o) {
-  const long long n = api().sgr_gn_resize_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, (int)s.Hs, (int)s.Ws, s.up(), backward);
-  TORCH_CHECK(n > 0, "sgrender: gn_resize: no workspace size for these sizes");
-  return at::empty({(int64_t)n}, o);
+  return workspace_floats(api().sgr_gn_resize_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, (int)s.Hs, (int)s.Ws, s.up(), backward), "gn_resize", o);
 }
 
 // -> (out, stats [B,G,4])
@@ -115,9 +108,8 @@ Resize check_bwd(const Tensor& g, const OT& x, const OT& weight, const OT& bias,
 }
 // a [0] tensor where a gradient is not wanted
 T4 bwd_outputs(const Resize& s, const at::TensorOptions& o, bool nX, bool nW, bool nB, bool nS) {
-  auto none = [&] { return at::empty({0}, o); };
-  return {nX ? at::empty({s.B, s.C, s.H, s.W}, o) : none(), nW ? at::empty({s.C}, o) : none(), nB ? at::empty({s.C}, o) : none(),
-          nS ? at::empty({s.B, s.Cs, s.Hs, s.Ws}, o) : none()};
+  return {nX ? at::empty({s.B, s.C, s.H, s.W}, o) : none(o), nW ? at::empty({s.C}, o) : none(o), nB ? at::empty({s.C}, o) : none(o),
+          nS ? at::empty({s.B, s.Cs, s.Hs, s.Ws}, o) : none(o)};
 }
 T4 gn_resize_bwd_cuda(const Tensor& g, const OT& x, const OT& weight, const OT& bias, const OT& stats, int64_t C, int64_t Cs, int64_t G, int64_t H, int64_t W, bool nX,
                       bool nW, bool nB, bool nS) {
@@ -175,9 +167,8 @@ struct GnResizeFn : public torch::autograd::Function<GnResizeFn> {
     if (!g[0].defined()) return out;
     const auto s = ctx->get_saved_variables();
     const bool need[4] = {ctx->saved_data["nX"].toBool(), ctx->saved_data["nW"].toBool(), ctx->saved_data["nB"].toBool(), ctx->saved_data["nS"].toBool()};
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     static auto bwd = find_op<BwdSig>("sgrender::gn_resize_bwd");
-    auto [dx, dw, db, ds] = bwd.call(g[0], opt(s[0]), opt(s[1]), opt(s[2]), opt(s[3]), ctx->saved_data["C"].toInt(), ctx->saved_data["Cs"].toInt(),
+    auto [dx, dw, db, ds] = bwd.call(g[0], opt_of(s[0]), opt_of(s[1]), opt_of(s[2]), opt_of(s[3]), ctx->saved_data["C"].toInt(), ctx->saved_data["Cs"].toInt(),
                                      ctx->saved_data["G"].toInt(), ctx->saved_data["H"].toInt(), ctx->saved_data["W"].toInt(), need[0], need[1], need[2], need[3]);
     if (need[0]) out[0] = dx;
     if (need[1]) out[1] = dw;

@@ -22,7 +22,6 @@ using BwdOut = std::tuple<TV, TV, TV, Tensor>;
 
 constexpr int64_t kMaxSiblings = SGR_GN_MAX_SIBLINGS;
 
-bool present(const Tensor& t) { return t.defined() && t.numel() > 0; }
 bool io_type(at::ScalarType t) { return t == at::kFloat || t == at::kBFloat16; }
 
 struct Sib {
@@ -117,10 +116,8 @@ TV contiguous(TL ts) {
 }
 
 Tensor workspace(const Sib& s, bool backward, const at::TensorOptions& of) {
-  const long long n = s.resize ? api().sgr_gn_resize_siblings_workspace_floats((int)s.D, (int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, (int)s.Hs, (int)s.Ws, backward)
-                               : api().sgr_gn_stage_siblings_workspace_floats((int)s.D, (int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, backward);
-  TORCH_CHECK(n > 0, "sgrender: ", s.who, ": no workspace size for these sizes");
-  return at::empty({(int64_t)n}, of);
+  return workspace_floats(s.resize ? api().sgr_gn_resize_siblings_workspace_floats((int)s.D, (int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, (int)s.Hs, (int)s.Ws, backward)
+                               : api().sgr_gn_stage_siblings_workspace_floats((int)s.D, (int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, backward), s.who, of);
 }
 
 // -> (outs, stats [D,B,G,4])

@@ -12,8 +12,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 // the element types of x, skip, the result, the cotangent, dx and dskip; everything else is fp32
 bool io_type(at::ScalarType t) { return t == at::kFloat || t == at::kBFloat16; }
 // a bf16 tensor's elements as the C ABI takes them; absent and empty tensors are NULL
@@ -70,13 +68,8 @@ Stage check_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias, const
   return s;
 }
 
-struct Strides4 { long long v[4]; };
-Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
-
 Tensor workspace(const Stage& s, bool backward, const at::TensorOptions& o) {
-  const long long n = api().sgr_gn_stage_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, s.up(), backward);
-  TORCH_CHECK(n > 0, "sgrender: gn_stage: no workspace size for these sizes");
-  return at::empty({(int64_t)n}, o);
+  return workspace_floats(api().sgr_gn_stage_workspace_floats((int)s.B, (int)s.C, (int)s.G, (int)s.H, (int)s.W, s.up(), backward), "gn_stage", o);
 }
 
 // -> (out, stats [B,G,4])
@@ -199,9 +192,8 @@ struct GnStageFn : public torch::autograd::Function<GnStageFn> {
     if (!g[0].defined()) return out;
     const auto s = ctx->get_saved_variables();
     const bool need[4] = {ctx->saved_data["nX"].toBool(), ctx->saved_data["nW"].toBool(), ctx->saved_data["nB"].toBool(), ctx->saved_data["nS"].toBool()};
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     static auto bwd = find_op<BwdSig>("sgrender::gn_stage_bwd");
-    auto [dx, dw, db, ds] = bwd.call(g[0], opt(s[0]), opt(s[1]), opt(s[2]), opt(s[3]), ctx->saved_data["C"].toInt(), ctx->saved_data["Cs"].toInt(),
+    auto [dx, dw, db, ds] = bwd.call(g[0], opt_of(s[0]), opt_of(s[1]), opt_of(s[2]), opt_of(s[3]), ctx->saved_data["C"].toInt(), ctx->saved_data["Cs"].toInt(),
                                      ctx->saved_data["G"].toInt(), need[0], need[1], need[2], need[3]);
     if (need[0]) out[0] = dx;
     if (need[1]) out[1] = dw;

@@ -11,8 +11,6 @@ namespace {
 using namespace sgr_host;
 using OT = OptTensor;
 
-bool has(const OT& t) { return t.has_value() && t->defined(); }
-
 constexpr int64_t kMaxO = 48, kMinC = 16, kMaxC = 256;      // kLfMaxO, kLfMinC, kLfMaxC of csrc/sgr_light_final_conv.h
 constexpr const char* kCompose = "; compose F.pad(., (1, 1, 1, 1), mode='replicate') and F.conv2d instead";
 
@@ -42,9 +40,6 @@ Conv check_fwd(const Tensor& y, const Tensor& weight, const Tensor& bias, bool d
   TORCH_CHECK(weight.device() == y.device() && bias.device() == y.device(), "sgrender: light_final_conv: tensors on different devices");
   return s;
 }
-
-struct Strides4 { long long v[4]; };
-Strides4 strides_of(const Tensor& t) { return {{(long long)t.stride(0), (long long)t.stride(1), (long long)t.stride(2), (long long)t.stride(3)}}; }
 
 Tensor light_final_conv_cuda(const Tensor& y, const Tensor& weight, const Tensor& bias) {
   const Conv s = check_fwd(y, weight, bias, true);
@@ -86,8 +81,7 @@ Conv check_bwd(const Tensor& g, const OT& y, const OT& weight, bool nY, bool nW,
 }
 // a [0] tensor where a gradient is not wanted
 T3 bwd_outputs(const Conv& s, const at::TensorOptions& o, bool nY, bool nW, bool nB) {
-  auto none = [&] { return at::empty({0}, o); };
-  return {nY ? at::empty({s.B, s.C, s.H, s.W}, o) : none(), nW ? at::empty({s.O, s.C, 3, 3}, o) : none(), nB ? at::empty({s.O}, o) : none()};
+  return {nY ? at::empty({s.B, s.C, s.H, s.W}, o) : none(o), nW ? at::empty({s.O, s.C, 3, 3}, o) : none(o), nB ? at::empty({s.O}, o) : none(o)};
 }
 T3 light_final_conv_bwd_cuda(const Tensor& g, const OT& y, const OT& weight, bool nY, bool nW, bool nB) {
   const Conv s = check_bwd(g, y, weight, nY, nW, nB, true);
@@ -100,9 +94,7 @@ T3 light_final_conv_bwd_cuda(const Tensor& g, const OT& y, const OT& weight, boo
   if (nY) w = weight->contiguous();
   if (nW) ys = strides_of(*y);
   if (nW || nB) {
-    const long long n = api().sgr_light_final_conv_workspace_floats((int)s.B, (int)s.C, (int)s.O, (int)s.H, (int)s.W);
-    TORCH_CHECK(n > 0, "sgrender: light_final_conv_bwd: no workspace size for these sizes");
-    ws = at::empty({(int64_t)n}, o);
+    ws = workspace_floats(api().sgr_light_final_conv_workspace_floats((int)s.B, (int)s.C, (int)s.O, (int)s.H, (int)s.W), "light_final_conv_bwd", o);
   }
   ok(api().sgr_light_final_conv_bwd(rp(gc), nW ? rp(*y) : nullptr, rp(w), wp(std::get<0>(out)), wp(std::get<1>(out)), wp(std::get<2>(out)), wp(ws), (int)s.B, (int)s.C,
                                     (int)s.O, (int)s.H, (int)s.W, nW ? ys.v : nullptr, stream_of(g.device())),
@@ -135,9 +127,8 @@ struct LightFinalConvFn : public torch::autograd::Function<LightFinalConvFn> {
     if (!g[0].defined()) return out;
     const auto s = ctx->get_saved_variables();
     const bool nY = ctx->saved_data["nY"].toBool(), nW = ctx->saved_data["nW"].toBool(), nB = ctx->saved_data["nB"].toBool();
-    auto opt = [](const Tensor& t) { return t.defined() ? OT(t) : OT(); };
     static auto bwd = find_op<BwdSig>("sgrender::light_final_conv_bwd");
-    auto [dy, dw, db] = bwd.call(g[0], opt(s[0]), opt(s[1]), nY, nW, nB);
+    auto [dy, dw, db] = bwd.call(g[0], opt_of(s[0]), opt_of(s[1]), nY, nW, nB);
     if (nY) out[0] = dy;
     if (nW) out[1] = dw;
     if (nB) out[2] = db;
