@@ -705,6 +705,21 @@ int sgr_encoder_conv_fwd(const float* x, const float* weight, const float* bias,
 int sgr_encoder_conv_bwd(const float* g, const float* x, const float* weight, float* dx, float* dweight, float* dbias, float* workspace,
                          int B, int C, int O, int H, int W, const long long* x_strides, int pad_mode, void* stream);
 
+/* The same convolution over S sources, 1 <= S <= SGR_ENCODER_CONV_MAX_SOURCES: the bits of sgr_encoder_conv_fwd / _bwd on the concatenation
+ * of the sources along the channels, which is never written.  xs[i] is [B, channels[i], H, W], fp32, read through strides[4 i .. 4 i + 3];
+ * channels[i] >= 1 and their sum C <= 160; weight [O,C,4,4].  xs, channels and strides are host arrays, read during the call: the table
+ * travels in the kernel arguments, so a call captures in a HIP graph.  The forward is one launch.  dxs[i], contiguous
+ * [B, channels[i], H, W], is the matching channel slice of the concatenation's dx; a NULL dxs[i] (or a NULL dxs) is not wanted, and its
+ * channels are in no launch's range: the data gradient and, in replicate mode, its border launch run once per source that wants one.  xs
+ * may be NULL when dweight is.  The workspace is sgr_encoder_conv_workspace_floats(B, C, O, H, W) floats.  S == 1 is sgr_encoder_conv_fwd /
+ * _bwd, launch for launch.  Refusals return SGR_ERR_UNSUPPORTED with a message that names torch.cat(xs, 1) + F.pad + F.conv2d, and launch
+ * nothing. */
+#define SGR_ENCODER_CONV_MAX_SOURCES 4
+int sgr_encoder_conv_cat_fwd(int S, const float* const* xs, const int* channels, const long long* strides, const float* weight, const float* bias,
+                             float* out, int B, int O, int H, int W, int pad_mode, void* stream);
+int sgr_encoder_conv_cat_bwd(int S, const float* g, const float* const* xs, const int* channels, const long long* strides, const float* weight,
+                             float* const* dxs, float* dweight, float* dbias, float* workspace, int B, int O, int H, int W, int pad_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,12 @@ from .gn_stage import GroupNormReLU, group_norm_relu, group_norm_relu_resize, gr
 from .gn_stage import SiblingGroupNormReLU, group_norm_relu_resize_upcat_siblings, group_norm_relu_upcat_siblings  # noqa: F401
 from .final_conv import FinalConv, final_conv, group_norm_relu_final_conv  # noqa: F401
 from .light_final_conv import LightFinalConv, light_final_conv  # noqa: F401
-from .encoder_conv import EncoderConv, encoder_conv  # noqa: F401
+from .encoder_conv import EncoderConv, encoder_conv, encoder_conv_cat  # noqa: F401
 from .graphs import CapturedStep, capture_step  # noqa: F401
 from .handoff import loadH5, read_cascade_handoff, write_cascade_handoff, writeH5ToFile  # noqa: F401
 from .losses import (LSregress, LSregressDiffSpec, combine_loss_parts, ddp_loss_scale, disable_native_allreduce,  # noqa: F401
                      enable_native_allreduce, light_objective, light_objective_supported, native_allreduce_enabled, recon_loss, render_loss)
 
-__all__ = ["encoder_conv", "EncoderConv", "light_final_conv", "LightFinalConv", "final_conv", "group_norm_relu_final_conv", "FinalConv", "group_norm_relu", "group_norm_relu_upcat", "group_norm_relu_resize", "group_norm_relu_resize_upcat", "GroupNormReLU", "group_norm_relu_upcat_siblings", "group_norm_relu_resize_upcat_siblings", "SiblingGroupNormReLU", "brdf_heads", "brdf_head", "brdf_encoder_input", "brdf_objective", "batch_ranking_loss", "BRDFObjective", "BilateralLayer", "bilateral_solve", "BILATERAL_MODES", "light_albedo_scale", "light_encoder_input", "light_heads", "unpack_envmaps", "output2env", "renderingLayer", "render_from_sg", "renderLayer", "output_radiance", "predToShading",
+__all__ = ["encoder_conv", "encoder_conv_cat", "EncoderConv", "light_final_conv", "LightFinalConv", "final_conv", "group_norm_relu_final_conv", "FinalConv", "group_norm_relu", "group_norm_relu_upcat", "group_norm_relu_resize", "group_norm_relu_resize_upcat", "GroupNormReLU", "group_norm_relu_upcat_siblings", "group_norm_relu_resize_upcat_siblings", "SiblingGroupNormReLU", "brdf_heads", "brdf_head", "brdf_encoder_input", "brdf_objective", "batch_ranking_loss", "BRDFObjective", "BilateralLayer", "bilateral_solve", "BILATERAL_MODES", "light_albedo_scale", "light_encoder_input", "light_heads", "unpack_envmaps", "output2env", "renderingLayer", "render_from_sg", "renderLayer", "output_radiance", "predToShading",
            "LSregress", "LSregressDiffSpec", "render_loss", "recon_loss", "combine_loss_parts", "ddp_loss_scale", "light_objective",
            "light_objective_supported", "enable_native_allreduce", "disable_native_allreduce", "native_allreduce_enabled", "capture_step", "CapturedStep", "writeH5ToFile", "loadH5", "write_cascade_handoff", "read_cascade_handoff", "SgrenderError", "SgrenderUnavailable"]

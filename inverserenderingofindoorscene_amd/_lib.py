@@ -126,6 +126,8 @@ SIGNATURES = {
     "sgr_encoder_conv_workspace_floats": ([_I] * 5, c_longlong),
     "sgr_encoder_conv_fwd": ([_P] * 4 + [_I] * 5 + [_P, _I, _P], c_int),
     "sgr_encoder_conv_bwd": ([_P] * 7 + [_I] * 5 + [_P, _I, _P], c_int),
+    "sgr_encoder_conv_cat_fwd": ([_I] + [_P] * 6 + [_I] * 5 + [_P], c_int),
+    "sgr_encoder_conv_cat_bwd": ([_I] + [_P] * 9 + [_I] * 5 + [_P], c_int),
 }
 
 _lib = None

@@ -24,6 +24,48 @@ SGR_HD int ec_src(int t, int n, int mode) {
 }
 SGR_HD int ec_out(int n) { return n >> 1; }      // floor((n + 2 - 4) / 2) + 1 for n >= 2
 
+// ---- several sources: the convolution of their concatenation along the channels, which is never written ------------------------------------
+// Source i holds the channels first .. first + C_i - 1 of the concatenation and is read through its own four strides.  The table travels in
+// the kernel arguments (S <= 4); an unused entry has first = kEcNoSource, which no channel reaches.  The chunks, blocks and passes of the
+// tile loops below are those of the concatenation, so a chunk may hold channels of two sources: the source is looked up per channel, where
+// the channel is uniform across a wave (a scalar select chain, no indexed copy of the table).
+// WHY THE BITS ARE THOSE OF THE CONCATENATION: which tensor a number is read from does not enter any ORDER below.  The forward and the
+// weight gradient keep the concatenation's chunk and block boundaries, so every chain has the same terms in the same order.  The data
+// gradient's chain of one element runs over k = (o, tap) only -- no channel is summed -- so a launch over one source's channel range
+// (channel base `first`, the weight's row length still the total channel count) writes the bits of that slice of the concatenation's dx,
+// whatever 64-channel pass the channel falls in.
+constexpr int kEcMaxSources = 4;
+constexpr int kEcNoSource = 0x7fffffff;
+struct EcSource {
+  const float* p;
+  long long sb, sc, sh, sw;      // element strides of [B, C_i, H, W]
+  int first;                     // the source's first channel in the concatenation
+};
+struct EcSources { EcSource s[kEcMaxSources]; };
+// the source of channel c (0 <= c < the total): the last one whose first channel is <= c
+SGR_HD EcSource ec_source_of(const EcSources& t, int c) {
+  const float* p = t.s[0].p;
+  long long sb = t.s[0].sb, sc = t.s[0].sc, sh = t.s[0].sh, sw = t.s[0].sw;
+  int first = t.s[0].first;
+#pragma unroll
+  for (int i = 1; i < kEcMaxSources; ++i) {      // field by field: selects on scalars, never a copy of the table
+    const bool hit = c >= t.s[i].first;
+    p = hit ? t.s[i].p : p;
+    sb = hit ? t.s[i].sb : sb;
+    sc = hit ? t.s[i].sc : sc;
+    sh = hit ? t.s[i].sh : sh;
+    sw = hit ? t.s[i].sw : sw;
+    first = hit ? t.s[i].first : first;
+  }
+  return EcSource{p, sb, sc, sh, sw, first};
+}
+// plane (b, c) of the concatenation: where it starts, in its source
+SGR_HD const float* ec_source_plane(const EcSource& s, int b, int c) { return s.p + (long long)b * s.sb + (long long)(c - s.first) * s.sc; }
+// element (sr, sc) of a plane of source s; sr or sc < 0 is an absent pad element (zeros mode): an exact zero.  Fits 31 bits (host check)
+SGR_HD float ec_source_at(const EcSource& s, const float* plane, int sr, int sc) {
+  return (sr < 0 || sc < 0) ? 0.0f : plane[(unsigned)sr * (unsigned)s.sh + (unsigned)sc * (unsigned)s.sw];
+}
+
 // R_n(h) = {(i, k): 0 <= i < n div 2, 0 <= k < 4, src(2 i + k - 1, n) == h}: never more than two members.  Slot 0 is the tap of h's own
 // parity class k0 = (h + 1) & 1, slot 1 the tap k0 + 2; i = -1 marks a slot without a member.  In replicate mode row 0 gains (0, 0) and
 // the last row of an even map gains (n/2 - 1, 3): the other parity's taps, in the slot the class leaves empty there.

@@ -14,31 +14,16 @@
 // channels, up to 64 outputs and a strip of 25 16 x 4 pixel tiles; the strip's fp32 partial goes to the workspace with ordinary vector
 // stores and a second launch folds the partials in double in index order.  Backward, bias, two launches on the vector ALU:
 // sgr_final_conv.hip's scheme.  No atomics anywhere: two runs give the same bits.
-#include "sgr_encoder_conv.h"
-#include "sgr_launch.h"
-#include "sgr_reduce.h"        // block_sum, wave_sum, Vec<4>, aligned16
+#include "sgr_encoder_conv_wgrad.inl"      // the shared prelude (kEcThreads, EcStrides, ec_mfma, the CAT flag) and ec_bwd_w_kernel
 
 namespace sgr {
 
-constexpr int kEcThreads = 256;
-constexpr unsigned kEcAbsent = 0xffffffffu;      // the offset of a zeros-mode pad element
-
-struct EcStrides { long long b, c, h, w; };
-using ec_f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ ec_f32x4 ec_mfma(float a, float b, ec_f32x4 c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#else
-  return c;
-#endif
-}
-
 // grid (tiles, B, passes of 64 outputs).  NT: N tiles of the largest pass; a tile past a pass's outputs holds zero weights and is not stored
-template <int NT, bool VEC>
+template <int NT, bool VEC, typename... Tab>
 __global__ __launch_bounds__(kEcThreads) void ec_fwd_kernel(const float* __restrict__ x, EcStrides xs, const float* __restrict__ Wt,
                                                             const float* __restrict__ bias, float* __restrict__ out, int C, int O, int H, int W,
-                                                            int tilesX, int mode) {
+                                                            int tilesX, int mode, Tab... tab) {
+  constexpr bool CAT = sizeof...(Tab) == 1;
   constexpr int kHalo = kEcRows * kEcCols, kALoads = (kHalo + kEcThreads - 1) / kEcThreads;
   constexpr int kWElems = 16 * kEcKC * kEcPassO, kWLoads = kWElems / kEcThreads;
   __shared__ float at[kEcKC * kEcCHP];
@@ -50,14 +35,19 @@ __global__ __launch_bounds__(kEcThreads) void ec_fwd_kernel(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // what this thread carries from HBM to LDS for every channel: element e = tid + 256 k of the 18 x 66 halo tile
   unsigned off[kALoads];
-  int lidx[kALoads];
+  int lidx[kALoads], srow[kALoads], scol[kALoads];      // CAT: the source row and column; the offset waits for the channel's strides
 #pragma unroll
   for (int k = 0; k < kALoads; ++k) {
     const int e = tid + k * kEcThreads;
     const bool valid = e < kHalo;
     const int r = valid ? e / kEcCols : 0, tc = valid ? e - r * kEcCols : 0;
     const int sr = ec_src(2 * i0 - 1 + r, H, mode), sc = ec_src(2 * j0 - 1 + tc, W, mode);
-    off[k] = (sr < 0 || sc < 0) ? kEcAbsent : (unsigned)sr * (unsigned)xs.h + (unsigned)sc * (unsigned)xs.w;      // fits 31 bits (host check)
+    if constexpr (CAT) {
+      srow[k] = sr;
+      scol[k] = sc;
+    } else {
+      off[k] = (sr < 0 || sc < 0) ? kEcAbsent : (unsigned)sr * (unsigned)xs.h + (unsigned)sc * (unsigned)xs.w;      // fits 31 bits (host check)
+    }
     lidx[k] = valid ? ec_fwd_tile_idx(0, r, tc) : -1;
   }
   const float* xb = x + (long long)b * xs.b;
@@ -66,9 +56,17 @@ __global__ __launch_bounds__(kEcThreads) void ec_fwd_kernel(const float* __restr
 #pragma unroll
     for (int cc = 0; cc < kEcKC; ++cc) {
       const bool live = c0 + cc < C;      // past the last channel: a plane of zeros
-      const float* xp = xb + (long long)(live ? c0 + cc : 0) * xs.c;
+      if constexpr (CAT) {
+        // the channel is the loop's, so the lookup is uniform across the wave; a chunk may hold channels of two sources
+        const EcSource src = ec_source_of(ec_only(tab...), live ? c0 + cc : 0);
+        const float* xp = ec_source_plane(src, b, live ? c0 + cc : 0);
 #pragma unroll
-      for (int k = 0; k < kALoads; ++k) ra[cc][k] = (live && lidx[k] >= 0 && off[k] != kEcAbsent) ? xp[off[k]] : 0.0f;
+        for (int k = 0; k < kALoads; ++k) ra[cc][k] = (live && lidx[k] >= 0) ? ec_source_at(src, xp, srow[k], scol[k]) : 0.0f;
+      } else {
+        const float* xp = xb + (long long)(live ? c0 + cc : 0) * xs.c;
+#pragma unroll
+        for (int k = 0; k < kALoads; ++k) ra[cc][k] = (live && lidx[k] >= 0 && off[k] != kEcAbsent) ? xp[off[k]] : 0.0f;
+      }
     }
     // the chunk's weights of output o are 64 consecutive floats of Wt, [cc][kh][kw] = q; element e = tid + 256 k is (q = e >> 6, o = e & 63)
 #pragma unroll
@@ -148,10 +146,16 @@ __global__ __launch_bounds__(kEcThreads) void ec_fwd_kernel(const float* __restr
   }
 }
 
-// grid (tiles of the (a, b) grid, B, passes of 64 channels).  NT: N tiles of the largest pass; a channel past C has zero weights and is not stored
-template <int NT, bool VEC>
+// grid (tiles of the (a, b) grid, B, passes of 64 channels).  NT: N tiles of the largest pass; a channel past C has zero weights and is not stored.
+// CAT: dx [B, C, H, W] is one source's, and `range` places its channels in Wt
+template <int NT, bool VEC, typename... Range>
 __global__ __launch_bounds__(kEcThreads) void ec_bwd_data_kernel(const float* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ dx, int C,
-                                                                 int O, int H, int W, int tilesX) {
+                                                                 int O, int H, int W, int tilesX, Range... range) {
+  int cbase = 0, Ct = C;
+  if constexpr (sizeof...(Range) == 1) {
+    cbase = ec_only(range...).cbase;
+    Ct = ec_only(range...).Ct;
+  }
   constexpr int kGElems = kEcDOC * kEcDGPlane, kGLoads = (kGElems + kEcThreads - 1) / kEcThreads;
   constexpr int kWElems = kEcDOC * 16 * kEcDPassC, kWLoads = kWElems / kEcThreads;
   __shared__ float gt[kEcDOC * kEcDGPlane];
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(kEcThreads) void ec_bwd_data_kernel(const float* __
 #pragma unroll
     for (int k = 0; k < kWLoads; ++k) {
       const int e = tid + k * kEcThreads, oc = e >> 10, tap = (e >> 6) & 15, c = e & 63;
-      rw[k] = c < ncp ? Wt[((long long)(og + oc) * C + c0p + c) * 16 + tap] : 0.0f;
+      rw[k] = c < ncp ? Wt[((long long)(og + oc) * Ct + cbase + c0p + c) * 16 + tap] : 0.0f;
     }
   };
   auto put = [&]() {
@@ -268,9 +272,10 @@ __global__ __launch_bounds__(kEcThreads) void ec_bwd_data_kernel(const float* __
   }
 }
 
-// replicate mode: the 2 W + 2 (H - 2) pixels of the first and last row and column of every channel, one thread each.  grid (.., B)
-__global__ __launch_bounds__(kEcThreads) void ec_bwd_data_border_kernel(const float* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ dx, int C,
-                                                                        int O, int H, int W) {
+// replicate mode: the 2 W + 2 (H - 2) pixels of the first and last row and column of every channel, one thread each.  grid (.., B).
+// dx [B, C, H, W]; its channels are cbase .. cbase + C - 1 of the Ct channels of Wt (the single-source kernel: 0 and C)
+__device__ __forceinline__ void ec_bwd_data_border_body(const float* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ dx, int C, int O, int H,
+                                                        int W, int cbase, int Ct) {
   const int ring = 2 * W + 2 * (H - 2);
   const long long e = (long long)blockIdx.x * kEcThreads + threadIdx.x;
   if (e >= (long long)ring * C) return;
@@ -280,99 +285,15 @@ __global__ __launch_bounds__(kEcThreads) void ec_bwd_data_border_kernel(const fl
   else if (t < 2 * W) { h = H - 1; w = t - W; }
   else { const int u = t - 2 * W; h = 1 + (u >> 1); w = (u & 1) ? W - 1 : 0; }
   const int Ho = ec_out(H), Wo = ec_out(W);
-  dx[(((long long)b * C + c) * H + h) * W + w] = ec_dx_border(g + (long long)b * O * Ho * Wo, Wt, c, h, w, C, O, H, W);
+  dx[(((long long)b * C + c) * H + h) * W + w] = ec_dx_border(g + (long long)b * O * Ho * Wo, Wt, cbase + c, h, w, Ct, O, H, W);
 }
-
-// grid (strips of 25 pixel tiles, channel blocks x output passes, B).  partial[(((b S + strip) C + c) 16 + tap) O + o].  NT: N tiles of the
-// largest pass, CW: channels per wave of the largest block; a channel past C is a plane of zeros, an output past O a zero cotangent, and
-// neither is stored
-template <int NT, int CW>
-__global__ __launch_bounds__(kEcThreads) void ec_bwd_w_kernel(const float* __restrict__ g, const float* __restrict__ x, EcStrides xs, float* __restrict__ partial,
-                                                              int C, int O, int H, int W, int tilesX, int tiles, int opasses, int mode) {
-  constexpr int kHalo = kEcWRows * kEcWCols, kXElems = kEcWCB * kHalo, kXLoads = (kXElems + kEcThreads - 1) / kEcThreads;
-  constexpr int kGLoads = kEcPassO * 64 / kEcThreads;
-  __shared__ float xt[kEcWCB * kEcWCHP];
-  __shared__ float gtl[kEcPassO * kEcWGP];
-  const int Ho = ec_out(H), Wo = ec_out(W);
-  const int strip = blockIdx.x, cblk = blockIdx.y / opasses, opass = blockIdx.y - cblk * opasses, b = blockIdx.z;
-  const int c0 = cblk * kEcWCB, ncb = min(kEcWCB, C - c0), o0 = opass * kEcPassO, nnt = min(kEcPassNT, (O - o0) / 16);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t0 = strip * kEcWStrip, t1 = min(t0 + kEcWStrip, tiles);
-  const float* xb = x + (long long)b * xs.b + (long long)c0 * xs.c;
-  const float* gb = g + ((long long)b * O + o0) * Ho * Wo;
-  float rx[kXLoads], rg[kGLoads];
-  auto fetch = [&](int t) {
-    const int tyi = t / tilesX, j0 = (t - tyi * tilesX) * kEcWW, i0 = tyi * kEcWH;
-#pragma unroll
-    for (int k = 0; k < kXLoads; ++k) {
-      const int e = tid + k * kEcThreads, cc = e / kHalo, r2 = e - cc * kHalo, r = r2 / kEcWCols, tc = r2 - r * kEcWCols;
-      const int sr = ec_src(2 * i0 - 1 + r, H, mode), sc = ec_src(2 * j0 - 1 + tc, W, mode);
-      rx[k] = (e < kXElems && cc < ncb && sr >= 0 && sc >= 0) ? xb[(long long)cc * xs.c + (unsigned)sr * (unsigned)xs.h + (unsigned)sc * (unsigned)xs.w] : 0.0f;
-    }
-    // pixel p = tid & 63 of the tile, outputs (tid >> 6) + 4 k; outside the map and past the pass's outputs: exact zeros
-    const int p = tid & 63, gy = i0 + (p >> 4), gx = j0 + (p & 15);
-    const bool in = gy < Ho && gx < Wo;
-#pragma unroll
-    for (int k = 0; k < kGLoads; ++k) {
-      const int o = (tid >> 6) + 4 * k;
-      rg[k] = (in && o < 16 * nnt) ? gb[((long long)o * Ho + gy) * Wo + gx] : 0.0f;
-    }
-  };
-  auto put = [&]() {
-#pragma unroll
-    for (int k = 0; k < kXLoads; ++k) {
-      const int e = tid + k * kEcThreads, cc = e / kHalo, r2 = e - cc * kHalo, r = r2 / kEcWCols, tc = r2 - r * kEcWCols;
-      if (e < kXElems) xt[ec_w_x_idx(cc, r, tc)] = rx[k];
-    }
-#pragma unroll
-    for (int k = 0; k < kGLoads; ++k) gtl[ec_w_g_idx((tid >> 6) + 4 * k, tid & 63)] = rg[k];
-  };
-  ec_f32x4 run[CW][NT];
-#pragma unroll
-  for (int a = 0; a < CW; ++a)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) run[a][n] = ec_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  fetch(t0);
-#pragma unroll 1
-  for (int t = t0; t < t1; ++t) {
-    __syncthreads();      // the previous tile's readers are done
-    put();
-    __syncthreads();
-    if (t + 1 < t1) fetch(t + 1);      // in flight while tile t is consumed
-    ec_f32x4 acc[CW][NT];
-#pragma unroll
-    for (int a = 0; a < CW; ++a)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) acc[a][n] = ec_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      float bv[NT], av[CW];
-#pragma unroll
-      for (int n = 0; n < NT; ++n) bv[n] = gtl[ec_w_b_addr(lane, s, n)];
-#pragma unroll
-      for (int a = 0; a < CW; ++a) av[a] = xt[ec_w_a_addr(lane, s, wave + 4 * a)];
-#pragma unroll
-      for (int a = 0; a < CW; ++a)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[a][n] = ec_mfma(av[a], bv[n], acc[a][n]);
-    }
-#pragma unroll
-    for (int a = 0; a < CW; ++a)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) run[a][n] += acc[a][n];
-  }
-  float* pw = partial + ((long long)b * gridDim.x + strip) * C * 16 * O;
-#pragma unroll
-  for (int a = 0; a < CW; ++a) {
-    const int cc = wave + 4 * a;
-    if (cc >= ncb) continue;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-      if (n >= nnt) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pw[((long long)(c0 + cc) * 16 + lf_d_row(lane, r)) * O + o0 + 16 * n + lf_d_col(lane)] = run[a][n][r];
-    }
-  }
+__global__ __launch_bounds__(kEcThreads) void ec_bwd_data_border_kernel(const float* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ dx, int C,
+                                                                        int O, int H, int W) {
+  ec_bwd_data_border_body(g, Wt, dx, C, O, H, W, 0, C);
+}
+__global__ __launch_bounds__(kEcThreads) void ec_bwd_data_border_cat_kernel(const float* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ dx, int C,
+                                                                            int O, int H, int W, int cbase, int Ct) {
+  ec_bwd_data_border_body(g, Wt, dx, C, O, H, W, cbase, Ct);
 }
 
 // One thread per element e = (c 16 + tap) O + o of a partial: dWt[o, c, tap] = the sum over the P = B S partials, in double, in index order
@@ -423,14 +344,16 @@ static bool ec_sizes_ok(int B, int C, int O, int H, int W) {
 }
 
 #define EC_COMPOSE "; compose F.pad(x, (1, 1, 1, 1), mode=...) and F.conv2d(., stride=2) instead"
-#define EC_CHECK_SIZES(who)                                                                                                                  \
+// `compose`: the composition a refusal names
+#define EC_CHECK_SIZES_C(who, compose)                                                                                                           \
   SGR_REQUIRE(B > 0 && C > 0 && O > 0 && H > 0 && W > 0, who ": non-positive size");                                                         \
-  SGR_SUPPORTED(pad_mode == kEcReplicate || pad_mode == kEcZeros, who ": pad_mode must be 0 (replicate) or 1 (zeros)" EC_COMPOSE);           \
-  SGR_SUPPORTED(C <= kEcMaxC, who ": more than 160 input channels (the deeper encoder layers are plain GEMMs with small zero-padded copies)" EC_COMPOSE); \
-  SGR_SUPPORTED(O >= kEcMinO && O <= kEcMaxO && O % 16 == 0, who ": the output channels must be a multiple of 16 in 16..128" EC_COMPOSE);    \
-  SGR_SUPPORTED(H >= 2 && W >= 2, who ": H and W must be at least 2" EC_COMPOSE);                                                            \
+  SGR_SUPPORTED(pad_mode == kEcReplicate || pad_mode == kEcZeros, who ": pad_mode must be 0 (replicate) or 1 (zeros)" compose);           \
+  SGR_SUPPORTED(C <= kEcMaxC, who ": more than 160 input channels (the deeper encoder layers are plain GEMMs with small zero-padded copies)" compose); \
+  SGR_SUPPORTED(O >= kEcMinO && O <= kEcMaxO && O % 16 == 0, who ": the output channels must be a multiple of 16 in 16..128" compose);    \
+  SGR_SUPPORTED(H >= 2 && W >= 2, who ": H and W must be at least 2" compose);                                                            \
   SGR_SUPPORTED(B <= 65535, who ": B > 65535");                                                                                              \
   SGR_SUPPORTED((long long)ec_out(H) * ec_out(W) < (1ll << 26), who ": Ho * Wo out of range")
+#define EC_CHECK_SIZES(who) EC_CHECK_SIZES_C(who, EC_COMPOSE)
 
 }  // namespace sgr
 
@@ -517,4 +440,111 @@ extern "C" int sgr_encoder_conv_bwd(const float* g, const float* x, const float*
     hipLaunchKernelGGL(ec_bwd_b_fold_kernel, dim3(O), dim3(64), 0, st, partial_b, dbias, B, O, S);
   }
   return sgr_check((int)hipGetLastError(), "sgr_encoder_conv_bwd");
+}
+
+// ---- several sources ("several sources") -----------------------------------------------------------------------------
+#define EC_CAT_COMPOSE "; compose torch.cat(xs, 1), F.pad(x, (1, 1, 1, 1), mode=...) and F.conv2d(., stride=2) instead"
+
+// the checks both entry points share: the list, the channel counts and (where the sources are read) their strides.  C: the summed channels
+#define EC_CAT_CHECK_LIST(who)                                                                                                               \
+  SGR_SUPPORTED(S >= 1 && S <= kEcMaxSources, who ": the number of sources must be 1 .. 4" EC_CAT_COMPOSE);                                  \
+  SGR_REQUIRE(channels, who ": NULL tensor");                                                                                                \
+  int C = 0;                                                                                                                                 \
+  for (int i = 0; i < S; ++i) {                                                                                                              \
+    SGR_REQUIRE(channels[i] > 0, who ": non-positive size");                                                                                 \
+    SGR_SUPPORTED(channels[i] <= kEcMaxC, who ": more than 160 input channels (the deeper encoder layers are plain GEMMs with small zero-padded copies)" EC_CAT_COMPOSE); \
+    C += channels[i];                                                                                                                        \
+  }
+
+static EcSources ec_table(int S, const float* const* xs, const int* channels, const long long* strides) {
+  EcSources tab{};
+  int first = 0;
+  for (int i = 0; i < kEcMaxSources; ++i) {
+    if (i < S) {
+      tab.s[i] = EcSource{xs[i], strides[4 * i], strides[4 * i + 1], strides[4 * i + 2], strides[4 * i + 3], first};
+      first += channels[i];
+    } else {
+      tab.s[i] = EcSource{nullptr, 0, 0, 0, 0, kEcNoSource};
+    }
+  }
+  return tab;
+}
+
+extern "C" int sgr_encoder_conv_cat_fwd(int S, const float* const* xs, const int* channels, const long long* strides, const float* weight, const float* bias,
+                                        float* out, int B, int O, int H, int W, int pad_mode, void* stream) {
+  EC_CAT_CHECK_LIST("sgr_encoder_conv_cat_fwd");
+  SGR_REQUIRE(xs && strides && weight && bias && out, "sgr_encoder_conv_cat_fwd: NULL tensor");
+  for (int i = 0; i < S; ++i) SGR_REQUIRE(xs[i], "sgr_encoder_conv_cat_fwd: NULL tensor");
+  if (S == 1) return sgr_encoder_conv_fwd(xs[0], weight, bias, out, B, C, O, H, W, strides, pad_mode, stream);      // launch for launch
+  EC_CHECK_SIZES_C("sgr_encoder_conv_cat_fwd", EC_CAT_COMPOSE);
+  for (int i = 0; i < S; ++i) SGR_SUPPORTED(ec_plane_fits(strides + 4 * i, H, W), "sgr_encoder_conv_cat_fwd: negative or out-of-range plane strides");
+  const EcSources tab = ec_table(S, xs, channels, strides);
+  const int Ho = ec_out(H), Wo = ec_out(W), tilesX = (Wo + kEcTW - 1) / kEcTW, tilesY = (Ho + kEcTH - 1) / kEcTH;
+  const dim3 grid(tilesX * tilesY, B, (O + kEcPassO - 1) / kEcPassO), block(kEcThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = Wo % 4 == 0 && aligned16({out});
+  const int NT = O >= kEcPassO ? kEcPassNT : O / 16;
+#define EC_FWD(N, V) hipLaunchKernelGGL((ec_fwd_kernel<N, V, EcSources>), grid, block, 0, st, (const float*)nullptr, EcStrides{}, weight, bias, out, C, O, H, W, tilesX, pad_mode, tab)
+#define EC_FWD_N(N) do { if (vec) EC_FWD(N, true); else EC_FWD(N, false); } while (0)
+  if (NT == 1) EC_FWD_N(1); else if (NT == 2) EC_FWD_N(2); else if (NT == 3) EC_FWD_N(3); else EC_FWD_N(4);
+#undef EC_FWD_N
+#undef EC_FWD
+  return sgr_check((int)hipGetLastError(), "sgr_encoder_conv_cat_fwd");
+}
+
+extern "C" int sgr_encoder_conv_cat_bwd(int S, const float* g, const float* const* xs, const int* channels, const long long* strides, const float* weight,
+                                        float* const* dxs, float* dweight, float* dbias, float* workspace, int B, int O, int H, int W, int pad_mode, void* stream) {
+  EC_CAT_CHECK_LIST("sgr_encoder_conv_cat_bwd");
+  SGR_REQUIRE(g, "sgr_encoder_conv_cat_bwd: NULL cotangent");
+  bool any_dx = false;
+  for (int i = 0; dxs && i < S; ++i) any_dx = any_dx || dxs[i];
+  SGR_REQUIRE(any_dx || dweight || dbias, "sgr_encoder_conv_cat_bwd: no gradient requested");
+  SGR_REQUIRE(!any_dx || weight, "sgr_encoder_conv_cat_bwd: NULL tensor");
+  SGR_REQUIRE(!dweight || (xs && strides), "sgr_encoder_conv_cat_bwd: NULL tensor");
+  for (int i = 0; dweight && i < S; ++i) SGR_REQUIRE(xs[i], "sgr_encoder_conv_cat_bwd: NULL tensor");
+  SGR_REQUIRE(!(dweight || dbias) || workspace, "sgr_encoder_conv_cat_bwd: NULL tensor");
+  if (S == 1) {      // launch for launch
+    return sgr_encoder_conv_bwd(g, dweight ? xs[0] : nullptr, weight, any_dx ? dxs[0] : nullptr, dweight, dbias, workspace, B, C, O, H, W, strides, pad_mode, stream);
+  }
+  EC_CHECK_SIZES_C("sgr_encoder_conv_cat_bwd", EC_CAT_COMPOSE);
+  for (int i = 0; dweight && i < S; ++i) SGR_SUPPORTED(ec_plane_fits(strides + 4 * i, H, W), "sgr_encoder_conv_cat_bwd: negative or out-of-range plane strides");
+  SGR_SUPPORTED(!any_dx || (long long)H * W < (1ll << 30), "sgr_encoder_conv_cat_bwd: H * W out of range for dx");
+  SGR_SUPPORTED(!dweight || (long long)B * ec_w_strips(H, W) < (1ll << 31), "sgr_encoder_conv_cat_bwd: B * Ho * Wo out of range for dweight");
+  hipStream_t st = (hipStream_t)stream;
+  const int Ho = ec_out(H), Wo = ec_out(W);
+  // the data gradient: one launch (two in replicate mode) per source that wants one, over that source's channels alone
+  for (int i = 0, cbase = 0; i < S; cbase += channels[i], ++i) {
+    float* dx = any_dx ? dxs[i] : nullptr;
+    if (!dx) continue;
+    const int Ci = channels[i];
+    const int tilesX = ((W + 1) / 2 + kEcDW - 1) / kEcDW, tilesY = ((H + 1) / 2 + kEcDH - 1) / kEcDH;
+    const dim3 grid(tilesX * tilesY, B, (Ci + kEcDPassC - 1) / kEcDPassC), block(kEcThreads);
+    const bool vec = W % 4 == 0 && aligned16({dx});
+    const int NT = Ci >= kEcDPassC ? kEcDPassNT : (Ci + 15) / 16;
+#define EC_DX(N, V) hipLaunchKernelGGL((ec_bwd_data_kernel<N, V, EcRange>), grid, block, 0, st, g, weight, dx, Ci, O, H, W, tilesX, EcRange{cbase, C})
+#define EC_DX_N(N) do { if (vec) EC_DX(N, true); else EC_DX(N, false); } while (0)
+    if (NT == 1) EC_DX_N(1); else if (NT == 2) EC_DX_N(2); else if (NT == 3) EC_DX_N(3); else EC_DX_N(4);
+#undef EC_DX_N
+#undef EC_DX
+    if (pad_mode == kEcReplicate) {
+      const long long n = (long long)(2 * W + 2 * (H - 2)) * Ci;
+      hipLaunchKernelGGL(ec_bwd_data_border_cat_kernel, dim3((unsigned)((n + kEcThreads - 1) / kEcThreads), B), block, 0, st, g, weight, dx, Ci, O, H, W, cbase, C);
+    }
+  }
+  if (dweight) {
+    const EcSources tab = ec_table(S, xs, channels, strides);
+    const int tilesX = (Wo + kEcWW - 1) / kEcWW, tiles = tilesX * ((Ho + kEcWH - 1) / kEcWH), strips = (int)ec_w_strips(H, W);
+    const int opasses = (O + kEcPassO - 1) / kEcPassO, cblocks = (C + kEcWCB - 1) / kEcWCB;
+    const int NT = O >= kEcPassO ? kEcPassNT : O / 16, CW = C >= kEcWCB ? kEcWCB / 4 : (C + 3) / 4;
+    ec_launch_w_cat(dim3(strips, cblocks * opasses, B), st, NT, CW, g, tab, workspace, C, O, H, W, tilesX, tiles, opasses, pad_mode);
+    const int n = C * 16 * O;
+    hipLaunchKernelGGL(ec_bwd_w_fold_kernel, dim3((n + kEcThreads - 1) / kEcThreads), dim3(kEcThreads), 0, st, workspace, dweight, B * strips, C, O);
+  }
+  if (dbias) {
+    const int Sl = (int)ec_b_slices(H, W);
+    float* partial_b = workspace + ec_w_floats(B, C, O, H, W);
+    hipLaunchKernelGGL(ec_bwd_b_kernel, dim3(Sl, O, B), dim3(kEcThreads), 0, st, g, partial_b, O, (long long)Ho * Wo);
+    hipLaunchKernelGGL(ec_bwd_b_fold_kernel, dim3(O), dim3(64), 0, st, partial_b, dbias, B, O, Sl);
+  }
+  return sgr_check((int)hipGetLastError(), "sgr_encoder_conv_cat_bwd");
 }

@@ -112,6 +112,7 @@ constexpr const char* kFp32Ops[] = {
     "brdf_encoder_input", "brdf_heads", "brdf_heads_bwd", "bilateral_grid", "bilateral_solve_fwd", "bilateral_solve_bwd", "bilateral_solve",
     // sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp (the resize form), sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp
     "gn_resize", "gn_resize_bwd", "gn_resize_siblings", "gn_resize_siblings_bwd", "final_conv", "final_conv_bwd", "light_final_conv", "light_final_conv_bwd", "encoder_conv", "encoder_conv_bwd",
+    "encoder_conv_cat", "encoder_conv_cat_bwd",
 };
 
 }  // namespace

@@ -59,7 +59,8 @@ using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Te
   X(sgr_gn_resize_siblings_workspace_floats) X(sgr_gn_resize_siblings_fwd) X(sgr_gn_resize_siblings_bwd)                            \
   X(sgr_gn_moments) X(sgr_final_conv_workspace_floats) X(sgr_final_conv_fwd) X(sgr_final_conv_bwd)                              \
   X(sgr_light_final_conv_workspace_floats) X(sgr_light_final_conv_fwd) X(sgr_light_final_conv_bwd)                        \
-  X(sgr_encoder_conv_workspace_floats) X(sgr_encoder_conv_fwd) X(sgr_encoder_conv_bwd)
+  X(sgr_encoder_conv_workspace_floats) X(sgr_encoder_conv_fwd) X(sgr_encoder_conv_bwd)                                    \
+  X(sgr_encoder_conv_cat_fwd) X(sgr_encoder_conv_cat_bwd)
 
 struct Api {
 #define SGR_DECL(name) decltype(&::name) name = nullptr;

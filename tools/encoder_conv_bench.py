@@ -7,6 +7,18 @@ two of them with a cascade-0 and a cascade-1 input width, forward and forward + 
 
     python tools/encoder_conv_bench.py [--reps 80] [--warmup 10] [--out FILE.json]
     rocprofv3 --kernel-trace --stats ... -- python tools/encoder_conv_bench.py --profile     # ours only, few repetitions
+    python tools/encoder_conv_bench.py --sources [--profile]     # the several-source leg alone (below)
+
+``--sources``: encoderLight.conv1 at cascade 1 as the reference feeds it -- the 64 ``preProcess`` channels and the 7 SGNum channels of
+``envmapsPreBatch`` as two tensors (models.py:254-262) -- at batch 16, 120x160, 128 outputs, replicate, splits (64, 84) and (64, 7):
+
+    cat_ours      sgr.encoder_conv_cat([x1, x2], Wt, bias)                        no concatenated copy
+    cat_then_ours sgr.encoder_conv(torch.cat([x1, x2], 1), Wt, bias)              what the single-source operator offers
+    eager         F.conv2d(F.pad(torch.cat([x1, x2], 1), ...), Wt, bias, stride=2)
+
+forward, and forward + backward with only the first source requiring grad (``first``: what trainLight.py at cascade 1 does -- the envmaps
+are data) and with both (``both``).  The floor is the single-source floor of the summed channels, with the data gradient's share scaled to
+the channels that want one.
 
 Method: device events around each call, warm-up, median of >= 80, the candidates alternating in one process; the min-max spread of the
 repetitions is printed beside each median.  encoder0.conv1 is measured without the data gradient, as in training (its input is the image).
@@ -45,6 +57,60 @@ def floors_us(C, O, H, W, need_dx):
     return fwd, fwd + bwd
 
 
+def sources_leg(sgr, args, rec):
+    """the --sources leg: three candidates alternating, forward / forward + backward (first source's dx only, both)"""
+    reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
+    O, H, W = 128, 120, 160
+    for split in ((64, 84), (64, 7)):
+        C = sum(split)
+        name = f"encoderLight.conv1_c1_{split[0]}+{split[1]}to{O}_{H}x{W}"
+        g = torch.Generator().manual_seed(C + O)
+        x1, x2 = (torch.randn(B, c, H, W, generator=g).cuda() for c in split)
+        Wt = (torch.randn(O, C, 4, 4, generator=g) / (16.0 * C) ** 0.5).cuda().requires_grad_(True)
+        bias = (0.1 * torch.randn(O, generator=g)).cuda().requires_grad_(True)
+        ct = torch.randn(B, O, H // 2, W // 2, generator=g).cuda()
+        cands = dict(cat_ours=lambda a, b: sgr.encoder_conv_cat([a, b], Wt, bias))
+        if not args.profile:
+            cands["cat_then_ours"] = lambda a, b: sgr.encoder_conv(torch.cat([a, b], 1), Wt, bias)
+            cands["eager"] = lambda a, b: F.conv2d(F.pad(torch.cat([a, b], 1), (1, 1, 1, 1), mode="replicate"), Wt, bias, stride=2)
+        a1, b1 = x1.clone().requires_grad_(True), x2.clone().requires_grad_(True)
+
+        def fwd(f):
+            def run():
+                with torch.no_grad():
+                    return f(x1, x2)
+            return run
+        fns = {}
+        for k, f in cands.items():
+            fns[f"{k}|fwd"] = fwd(f)
+            fns[f"{k}|fwd_bwd_first"] = lambda f=f: torch.autograd.grad(f(a1, x2), [a1, Wt, bias], grad_outputs=ct)
+            fns[f"{k}|fwd_bwd_both"] = lambda f=f: torch.autograd.grad(f(a1, b1), [a1, b1, Wt, bias], grad_outputs=ct)
+        t = timed(fns, reps, warm)
+        f_fwd, f_all = floors_us(C, O, H, W, True)
+        dx_share = floors_us(C, O, H, W, True)[1] - floors_us(C, O, H, W, False)[1]
+        floor = dict(fwd=f_fwd, fwd_bwd_first=f_all - dx_share * (1.0 - split[0] / C), fwd_bwd_both=f_all)
+        rec["floor_us"][name] = floor
+        for k, v in t.items():
+            med = statistics.median(v)
+            cand, what = k.split("|")
+            rec["ms"][f"{name}_{cand}_{what}"] = dict(median=med, min=v[0], max=v[-1])
+            note = f"floor {floor[what]:.0f} us (share {floor[what] / (med * 1e3):.2f})" if cand == "cat_ours" else ""
+            print(f"{name + ' ' + cand + ' ' + what:74s} median {med * 1e3:9.1f} us  min {v[0] * 1e3:9.1f}  max {v[-1] * 1e3:9.1f}  {note}", flush=True)
+        for what in floor if not args.profile else ():
+            ours = rec["ms"][f"{name}_cat_ours_{what}"]
+            for other in ("cat_then_ours", "eager"):
+                o = rec["ms"][f"{name}_{other}_{what}"]
+                s = o["median"] / ours["median"]
+                rec["ms"][f"{name}_speedup_{what}_vs_{other}"] = s
+                if s >= 1:
+                    verdict = "the difference exceeds the spread" if o["min"] > ours["max"] else "THE SPREADS OVERLAP"
+                else:
+                    verdict = "THE NEW CALL IS SLOWER" + ("" if ours["min"] > o["max"] else ", the spreads overlap")
+                print(f"{name + ' ' + what + ' vs ' + other:74s} {other} / cat_ours = {s:.2f}x  ({verdict})", flush=True)
+        del x1, x2, a1, b1, Wt, bias, ct
+        torch.cuda.empty_cache()
+
+
 def timed(fns, reps, warm):
     """{name: sorted ms} for the callables, alternating inside every repetition"""
     for _ in range(warm):
@@ -68,6 +134,7 @@ def main():
     ap.add_argument("--reps", type=int, default=80)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--sources", action="store_true", help="the several-source leg (sgr.encoder_conv_cat) instead of the single-source layers")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import inverserenderingofindoorscene_amd as sgr
@@ -75,7 +142,9 @@ def main():
         raise SystemExit("encoder_conv_bench needs a GPU")
     reps, warm = (5, 2) if args.profile else (max(80, args.reps), args.warmup)
     rec = {"device": torch.cuda.get_device_name(0), "reps": reps, "ms": {}, "floor_us": {}}
-    for layer, padding, C, O, H, W, need_dx in SHAPES:
+    if args.sources:
+        sources_leg(sgr, args, rec)
+    for layer, padding, C, O, H, W, need_dx in () if args.sources else SHAPES:
         name = f"{layer}_{C}to{O}_{H}x{W}"
         g = torch.Generator().manual_seed(C + O)
         x = torch.randn(B, C, H, W, generator=g).cuda().requires_grad_(need_dx)
