@@ -2,7 +2,9 @@
 
   * tests/brdf_input_checker.py (the contract of DESIGN.md section 8c in torch, own code) is pinned at 1e-12, in fp64, to the fixtures
     the UNMODIFIED reference produced (tests/golden/g15_brdfin_*.npz, tools/make_golden_brdf_input.py), and for the flag combination of
-    testReal.py:439-449 to the three ``F.interpolate`` / ``0.5 (x + 1)`` steps composed here;
+    testReal.py:439-449 to the three ``F.interpolate`` / ``0.5 (x + 1)`` steps composed here; at the seven geometries no fixture holds
+    (tests/brdf_input_cases.py) to ``F.interpolate``, ``F.adaptive_avg_pool2d`` and the regression written out here, again at 1e-12;
+  * every input set the GPU edge tests draw (same module, same seeds) decides neither discontinuity by rounding;
   * the C ABI refuses NULL tensors, non-positive sizes and an illegal source size before anything is dereferenced, and its workspace
     query is a pure host function;
   * ``torch.ops.sgrender.brdf_encoder_input`` is registered by the C++ extension with a Meta kernel of the documented shapes;
@@ -15,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import brdf_input_cases as K
 import brdf_input_checker as C
 from conftest import GOLDEN_DIR
 
@@ -80,6 +83,71 @@ def test_checker_matches_the_inference_form_composed_from_torch():
     assert err(out, want) <= PIN and bool((coef == 1).all())
     # and the pooling rule against torch's, at a non-integer ratio in both directions
     assert err(C.pooled(im, 7, 9), F.adaptive_avg_pool2d(im, (7, 9))) <= PIN
+
+
+def _torch_composition(im, al, nr, ro, dp, df, sp):
+    """the default call (regress, normalize, no remap) composed from torch's own resize and pooling, the regression of DESIGN.md section
+    8c written out image by image with plain branches"""
+    bn, _, H, W = im.shape
+    up = lambda t: t if tuple(t.shape[2:]) == (H, W) else F.interpolate(t, [H, W], mode="bilinear", align_corners=False)
+    small = F.adaptive_avg_pool2d(im, (df.shape[2], df.shape[3]))
+    n = df[0].numel()
+    dfs, sps, coef = [], [], []
+    for b in range(bn):
+        keep = (small[b] < 0.9).to(im.dtype)
+        d, s, i = df[b] * keep, sp[b] * keep, small[b] * keep
+        a11, a22, a12, b1, b2 = float((d * d).sum()), float((s * s).sum()), float((d * s).sum()), float((d * i).sum()), float((s * i).sum())
+        det = a11 * a22 - a12 * a12
+        if det / n > 1e-2:
+            cd, cs = (b1 * a22 - b2 * a12) / max(det, 1e-2), (a11 * b2 - b1 * a12) / max(det, 1e-2)
+        else:
+            cd, cs = min(max(b1 / max(a11, 1e-5), 1e-3), 1e3), 0.0
+        cd, cs = min(max(cd, 0.0), 1e3), min(max(cs, 0.0), 1e3)
+        render = torch.clamp(cd * df[b] + cs * sp[b], 0, 1)
+        cim = min(max(float((render * small[b]).sum()) / max(float((render * render).sum()), 1e-5), 1e-3), 1e3)
+        dfs.append(cim * (cd * df[b]))
+        sps.append(cim * (cs * sp[b]))
+        coef.append([cim * cd, cim * cs])
+    unit = lambda t: t / torch.clamp(t.flatten(1).mean(1), min=1e-10).reshape(-1, 1, 1, 1) / 3.0
+    out = torch.cat([im, unit(up(al)), up(nr), up(ro), unit(up(dp)), up(torch.stack(dfs)), up(torch.stack(sps))], 1)
+    return out, torch.tensor(coef, dtype=im.dtype)
+
+
+@pytest.mark.parametrize("name", list(K.GEOMETRIES))
+def test_checker_matches_torch_on_the_geometries_no_fixture_holds(name):
+    """maps equal along one axis only, a down-sample along one axis, an env grid at image size and one taller than the image, 1 x 1 maps:
+    the checker's own interpolation / pooling matrices against ``F.interpolate`` and ``F.adaptive_avg_pool2d``, in fp64 at PIN"""
+    inp = K.build(*K.GPU_CASES["geometry " + name])
+    args = K.tensors(inp, dtype=torch.float64)
+    H, W, h, w, R, Cc = K.GEOMETRIES[name]
+    assert tuple(args[0].shape[2:]) == (H, W) and tuple(args[1].shape[2:]) == (h, w) and tuple(args[5].shape[2:]) == (R, Cc)
+    out, coef = C.brdf_encoder_input(*args)
+    want, cw = _torch_composition(*args)
+    for g, (a, b) in C.GROUPS.items():
+        e = err(out[:, a:b], want[:, a:b])
+        assert e <= PIN, (name, g, e)
+    assert err(coef, cw) <= PIN, (name, coef, cw)
+    # and the inference form: remap, no regression, no normalisation (the remap before the resize: rounding only)
+    up = lambda t: t if tuple(t.shape[2:]) == (H, W) else F.interpolate(t, [H, W], mode="bilinear", align_corners=False)
+    im, al, nr, ro, dp, df, sp = args
+    want = torch.cat([im, up(al), 0.5 * (up(nr) + 1), 0.5 * (up(ro) + 1), up(dp), up(df), up(sp)], 1)
+    out, coef = C.brdf_encoder_input(*args, regress=False, normalize=False, remap=True)
+    assert err(out, want) <= PIN and bool((coef == 1).all())
+
+
+@pytest.mark.parametrize("tag", list(K.GPU_CASES))
+def test_inputs_of_the_gpu_edge_tests_decide_nothing_by_rounding(tag):
+    """every input set of tests/test_gpu_brdf_input_edges.py, built here from the same seeds: each pooled cell at least 1e-4 from the 0.9
+    mask, ``det / n`` at least 1e-5 from 1e-2 and on one side of it in fp32 and in fp64 -- what tools/make_golden_brdf_input.py asserts
+    of a fixture"""
+    inp = K.build(*K.GPU_CASES[tag])
+    gap, det = K.assert_settled(tag, inp)
+    assert all(v.dtype == np.float32 for v in inp.values())
+    assert (inp["diffusePre"][:, 0, 0, 0] == 1.0).all() and (inp["specularPre"][:, 0, 0, 0] == 0.25).all()
+    assert np.allclose(np.linalg.norm(inp["normalPre"], axis=1), 1.0, atol=1e-6)
+    assert inp["depthPre"].min() >= 0.5 and inp["depthPre"].max() <= 4.5
+    if tag == "tiny":
+        assert inp["diffusePre"][0].size < 64 and det[0] > 1e-2      # workgroups with no element; the two-coefficient branch
 
 
 def test_c_abi_refusals_and_workspace_without_gpu():
