@@ -294,6 +294,14 @@ template <> __device__ __forceinline__ void wait_vmcnt<24>() { asm volatile("s_w
 // env-sized rows of a 32-pixel tile by LDS-DMA: [3][32][16] floats (6 KB), 16-byte slots XOR-swizzled by (row >> 2) & 3
 constexpr int kPx = 32;
 constexpr int kT32Floats = 3 * kPx * 16;
+// The second request of a 32-pixel tile carries its +16 rows in the wave-uniform offset, which the range check of a raw buffer does not
+// cover: the check is  lane offset >= num_records - uniform offset,  and on the last tile of an image with R*C % 32 in 1..16 the
+// uniform offset of the last colour reaches num_records (the difference is 0: still all out of range) or passes it (the difference
+// wraps: nothing is out of range, and the masked rows would be read from behind the image).  Such a request -- no row of it lies in
+// the image, a wave-uniform fact -- is sent with a lane offset that no image reaches and no uniform offset instead: every lane fails the
+// check, the tile rows are filled with zeros, and the request still counts in vmcnt like any other.
+constexpr int kDmaPastImage = 0x7ffffff0;      // >= every num_records (a multiple of 192 below 2^31)
+__device__ __forceinline__ bool tile32_second_request_in_image(int p0, int RC) { return p0 + 16 < RC; }
 template <int AUX = SGR_DMA_AUX>
 __device__ __forceinline__ void tile32_dma_issue(float* tile, __amdgpu_buffer_rsrc_t rsrc, int p0, int RC, int J, int j0, int lane) {
   // Rows lrow and 16 + lrow carry the same swizzle ((row >> 2) & 3 is unchanged by + 16), so the second request's lane offset is the
@@ -303,13 +311,15 @@ __device__ __forceinline__ void tile32_dma_issue(float* tile, __amdgpu_buffer_rs
   const int lrow = lane >> 2, slot = lane & 3;
   const int col4 = slot ^ ((lrow >> 2) & 3);
   const int voff = (lrow * J + col4 * 4) * 4;                            // the lane's byte offset (32-bit)
+  const bool second = tile32_second_request_in_image(p0, RC);
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
+    const int v = (it == 0 || second) ? voff : kDmaPastImage;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int soff = (int)((((size_t)c * RC + p0 + it * 16) * J + j0) * 4);      // wave-uniform byte offset
       float* dst = tile + (c * kPx + it * 16) * 16;                      // wave-uniform, + lane*16 B implicitly
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)dst, 16, voff, soff, 0, AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)dst, 16, v, (it == 0 || second) ? soff : 0, 0, AUX);
     }
   }
 }

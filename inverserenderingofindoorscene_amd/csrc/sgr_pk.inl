@@ -415,6 +415,13 @@ __device__ __forceinline__ void shade_pair(const PixLocal& q, const OrthoPix& oq
 #ifndef SGR_PK_BWD_AUX
 #define SGR_PK_BWD_AUX 2   // cache policy of the packed backward's cotangent rows: 2 = non-temporal (read once)
 #endif
+#ifndef SGR_PK_BWD_ROWPAIR
+// sg_bwd_pk_kernel on the 16-wide grids: 1 = two table rows per pass of the azimuth-pair loop, 0 = one.  393 instead of 2 x 210 VALU
+// instructions per azimuth pair of a row pair and half the loop heads; 256 VGPRs, no scratch in the orthonormal loop (the
+// degenerate-frame loop reloads four registers per row pair).  Same-box A/B at config 2, profiles/r25_bwd_rowpair_ab.txt: the kernel
+// 225-226 -> 217-218 us, the forward + backward step 0.3665-0.3684 -> 0.3596-0.3607 ms.
+#define SGR_PK_BWD_ROWPAIR 1
+#endif
 #ifndef SGR_PK_BWD_FENCES
 #define SGR_PK_BWD_FENCES 2      // loop-body register fences of sg_bwd_pk_kernel: 2 = lobes, row constants, BRDF / cotangent constants; 1 = the first two
 #endif
@@ -611,14 +618,36 @@ __device__ __forceinline__ void tile32_dma_issue_vrow(float* tile, __amdgpu_buff
     const int ls = slot ^ ((lrow >> 2) & 3);                               // logical 16-byte slot this lane fills (rows lrow and 16 + lrow alike)
     const int col = 4 * ls + 8 * q + (ls >= 2 ? 8 : 0);                    // slots 0,1: half row 0; slots 2,3: half row 1
     const int voff = (lrow * J + col) * 4;                                 // one lane offset; the second request's 16 rows are wave-uniform (tile32_dma_issue)
+    const bool second = tile32_second_request_in_image(p0, RC);
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
+      const int v = (it == 0 || second) ? voff : kDmaPastImage;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const int soff = (int)((((size_t)c * RC + p0 + it * 16) * J + e * 32) * 4);
         float* dst = tile + (c * kPx + it * 16) * 16;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)dst, 16, voff, soff, 0, AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)dst, 16, v, (it == 0 || second) ? soff : 0, 0, AUX);
       }
+    }
+  }
+}
+// EW = 16, table rows in pairs (sg_bwd_pk_kernel): one tile = HALF A PASS over the row pair (e, e + 1) -- the azimuths [4 h, 4 h + 4) of
+// both half rows of both table rows, four 16-byte pieces of the pixel's 128-byte line (offsets 16 h + {0, 32, 64, 96}) gathered into
+// the same 16-float-per-pixel layout: logical slot 2 r + s holds row e + r, half row (sign) s.  `e` even.
+template <int AUX>
+__device__ __forceinline__ void tile32_dma_issue_rowpair(float* tile, __amdgpu_buffer_rsrc_t rsrc, int p0, int RC, int J, int e, int h, int lane) {
+  const int lrow = lane >> 2, slot = lane & 3;
+  const int ls = slot ^ ((lrow >> 2) & 3);                                 // logical 16-byte slot this lane fills (rows lrow and 16 + lrow alike)
+  const int voff = (lrow * J + 8 * ls) * 4;                                // (ls >> 1) * 16 + (ls & 1) * 8 floats into the pair's line
+  const bool second = tile32_second_request_in_image(p0, RC);
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int v = (it == 0 || second) ? voff : kDmaPastImage;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int soff = (int)((((size_t)c * RC + p0 + it * 16) * J + e * 16 + h * 4) * 4);
+      float* dst = tile + (c * kPx + it * 16) * 16;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LdsPtr)dst, 16, v, (it == 0 || second) ? soff : 0, 0, AUX);
     }
   }
 }
@@ -870,6 +899,28 @@ __device__ __forceinline__ void tile32_read_two_pairs2(const float* tile, int pl
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
+// a row-pair tile (tile32_dma_issue_rowpair): the pair (jj, jj + 1), jj in {0, 2}, of its four slots -- rows A and B, half rows 0 and 1 --
+// with a single wait (twelve reads in flight)
+__device__ __forceinline__ void tile32_read_four_pairs2(const float* tile, int pl, int jj, f32x2 (&gA0)[3], f32x2 (&gA1)[3], f32x2 (&gB0)[3],
+                                                        f32x2 (&gB1)[3]) {
+  const unsigned base = lds_addr(tile) + (unsigned)(pl * 64) + (unsigned)(jj * 4);
+  const unsigned sw = (unsigned)((pl >> 2) & 3);
+  const unsigned a0 = base + (0u ^ sw) * 16u, a1 = base + (1u ^ sw) * 16u, a2 = base + (2u ^ sw) * 16u, a3 = base + (3u ^ sw) * 16u;
+  asm volatile("ds_read_b64 %0, %1" : "=v"(gA0[0]) : "v"(a0) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gA0[1]) : "v"(a0), "n"(1 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gA0[2]) : "v"(a0), "n"(2 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1" : "=v"(gA1[0]) : "v"(a1) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gA1[1]) : "v"(a1), "n"(1 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gA1[2]) : "v"(a1), "n"(2 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1" : "=v"(gB0[0]) : "v"(a2) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gB0[1]) : "v"(a2), "n"(1 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gB0[2]) : "v"(a2), "n"(2 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1" : "=v"(gB1[0]) : "v"(a3) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gB1[1]) : "v"(a3), "n"(1 * kPx * 64) : "memory");
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(gB1[2]) : "v"(a3), "n"(2 * kPx * 64) : "memory");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
 
 // ============================== forwardEnv alone (env image read), packed half-wave (round 4) ======
 // The un-fused drop-in call renderingLayer.forwardEnv (models.py:461-522): HBM-bound (1672 B per shaded pixel in).  Round 1's
@@ -1030,9 +1081,18 @@ __global__ __launch_bounds__(kWave, 3) void render_genv_pk_half_kernel(const Arg
 template <int POOL, bool HAS_GENV, bool HAS_RENDER, int EW = 16, bool HEADS = false>
 __global__ __launch_bounds__(kWave, 2) void sg_bwd_pk_kernel(const Args a) {
   constexpr int HALF = 8, NP = 4, KPW = 6, Q = EW / 16;
-  // env cotangent rows: a ring of three one-row LDS-DMA buffers (18 KB).  Rows are requested two at a time, back to back
-  // (the two 64-byte halves of every 128-byte line of the image), one row ahead of their use; non-temporal, since the
-  // cotangent is read exactly once and must not push the SG parameters out of the Infinity Cache
+  // EW = 16: table rows are walked in pairs (e, e + 1) -- one pass of the azimuth-pair loop per pair, the row-independent terms
+  // (table entry, u per lobe, Pv) formed once -- with a lone last row when the row count is odd.  EW = 32: the two virtual rows
+  // of a table row use different azimuths and share nothing, so they stay one at a time.
+  constexpr bool PAIR = Q == 1 && SGR_PK_BWD_ROWPAIR;
+  // env cotangents: a ring of three 6 KB LDS-DMA buffers (18 KB), each holding one UNIT of the walk = NP / NR azimuth pairs' worth
+  // of cotangents for the NR rows of a pass.  One row at a time a unit is a (virtual) row; for a row pair it is HALF A PASS: the
+  // azimuths [4 h, 4 h + 4) of both half rows of both rows (tile32_dma_issue_rowpair) -- both rows of the pair are live for the whole
+  // pass, but each of the two tiles only for its half of it, so the third tile and the request points are those of the one-row walk
+  // and keep a whole unit of lead.  Units are requested two at a time, back to back (between them the two units of a pair cover every
+  // 128-byte line of the image once, like two rows do), one unit ahead of their use; non-temporal, since the cotangent is read exactly
+  // once and must not push the SG parameters out of the Infinity Cache.  Every unit is six requests, so every wait is a count of
+  // younger requests (6 per unit that may stay in flight).
   __shared__ __attribute__((aligned(16))) float tile[HAS_GENV ? 3 * kT32Floats : 4];
   SGR_TRACE_BEGIN
 
@@ -1050,9 +1110,15 @@ __global__ __launch_bounds__(kWave, 2) void sg_bwd_pk_kernel(const Args a) {
   const int nvr = a.eh * Q;                         // virtual rows
 
   __amdgpu_buffer_rsrc_t gimg = env_rsrc(HAS_GENV ? a.g_env + (size_t)b * 3 * RC * a.J : a.view, RC, a.J);
+  const int npu = PAIR ? (nvr & ~1) : 0;            // units [0, npu) are half passes of row pairs; a unit past them is the (virtual) row of its index
+  auto issue_unit = [&](int u) {
+    float* dst = tile + (u % 3) * kT32Floats;
+    if (PAIR && u < npu) tile32_dma_issue_rowpair<SGR_PK_BWD_AUX>(dst, gimg, x.p0, RC, a.J, u & ~1, u & 1, lane);
+    else tile32_dma_issue_vrow<SGR_PK_BWD_AUX, EW>(dst, gimg, x.p0, RC, a.J, u, lane);
+  };
   if (HAS_GENV && !(SGR_ABLATE & 1)) {
-    tile32_dma_issue_vrow<SGR_PK_BWD_AUX, EW>(tile, gimg, x.p0, RC, a.J, 0, lane);
-    if (nvr > 1) tile32_dma_issue_vrow<SGR_PK_BWD_AUX, EW>(tile + kT32Floats, gimg, x.p0, RC, a.J, 1, lane);
+    issue_unit(0);
+    if (nvr > 1) issue_unit(1);
   }
 
   PixLocal q;
@@ -1087,40 +1153,57 @@ __global__ __launch_bounds__(kWave, 2) void sg_bwd_pk_kernel(const Args a) {
   const XTable xt = (XTable)(a.cols + EW);
   SGR_TRACE_MARK
 
-  auto row_loop = [&](auto ortho_c) {
+  // one pass of the azimuth-pair loop over NR rows, starting at unit u0
+  auto pass = [&](auto ortho_c, auto nr_c, int u0) {
     constexpr bool ORTHO = decltype(ortho_c)::value;
-    for (int vr = 0; vr < nvr; ++vr) {
-      const int e = Q == 1 ? vr : (vr >> 1), aoff = Q == 1 ? 0 : (vr & 1) * NP;      // table row; first azimuth pair of this virtual row
-      const float* cur = tile + (HAS_GENV ? (vr % 3) * kT32Floats : 0);
+    constexpr int NR = decltype(nr_c)::value;      // rows of this pass = its units; NP / NR azimuth pairs per unit
+    static_assert(NR == 1 || Q == 1, "row pairs: EW = 16 only");
+    const int e0 = Q == 1 ? u0 : (u0 >> 1), aoff = Q == 1 ? 0 : (u0 & 1) * NP;      // first table row; first azimuth pair of a virtual row
+    if (HAS_RENDER && !ORTHO) fence_row_invariants(q);
+    float sr[NR], cr[NR];
+    f32x2 czr[NR][KPW / 2];
+    RowCtx rc[NR];
+    OrthoRow orow[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const f32x8 row = rows[e0 + r];
+      sr[r] = row[0]; cr[r] = row[1];
+#pragma unroll
+      for (int m = 0; m < KPW / 2; ++m) czr[r][m] = pfma(P.azp[m], splat2(cr[r]), -P.lpp[m]);      // lp (az c_e - 1)
+      rc[r] = make_row_ctx(q, row, HAS_RENDER);
+      orow[r] = make_ortho_row(rc[r].ro, q.vv);
+    }
+#pragma unroll 1
+    for (int h = 0; h < NR; ++h) {
+      const int u = u0 + h;
+      const float* cur = tile + (HAS_GENV ? (u % 3) * kT32Floats : 0);
       if (HAS_GENV && !(SGR_ABLATE & 1)) {
-        // rows vr+1, vr+2 (vr odd) were requested when row vr-1 was done; up to two rows (12 instructions) may stay in flight
-        if ((vr & 1) == 0) {
-          if (vr + 1 < nvr) wait_vmcnt<6>(); else wait_vmcnt<0>();          // in flight at most: row vr+1
+        // units u+1, u+2 (u odd) were requested when unit u-1 was done; up to two units (12 instructions) may stay in flight
+        if ((u & 1) == 0) {
+          if (u + 1 < nvr) wait_vmcnt<6>(); else wait_vmcnt<0>();          // in flight at most: unit u+1
         } else {
-          if (vr + 2 < nvr) wait_vmcnt<12>(); else if (vr + 1 < nvr) wait_vmcnt<6>(); else wait_vmcnt<0>();   // rows vr+1, vr+2
+          if (u + 2 < nvr) wait_vmcnt<12>(); else if (u + 1 < nvr) wait_vmcnt<6>(); else wait_vmcnt<0>();   // units u+1, u+2
         }
       }
-      if (HAS_RENDER && !ORTHO) fence_row_invariants(q);
-      const f32x8 row = rows[e];
-      const float sr = row[0], cr = row[1];
-      f32x2 czr[KPW / 2];
-#pragma unroll
-      for (int m = 0; m < KPW / 2; ++m) czr[m] = pfma(P.azp[m], splat2(cr), -P.lpp[m]);      // lp (az c_e - 1)
-      const RowCtx rc = make_row_ctx(q, row, HAS_RENDER);
-      OrthoRow orow = make_ortho_row(rc.ro, q.vv);
-
 #pragma unroll 1
-      for (int ap = 0; ap < NP; ++ap) {
+      for (int a2 = 0; a2 < NP / NR; ++a2) {
+        const int ap = h * (NP / NR) + a2;
         fence_lobes<KPW>(P);
 #pragma unroll
-        for (int m = 0; m < KPW / 2; ++m) { SGR_FENCE2(czr[m]); }
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+          for (int m = 0; m < KPW / 2; ++m) { SGR_FENCE2(czr[r][m]); }
 #if SGR_PK_BWD_FENCES >= 2
 #pragma unroll
         for (int m = 0; m < KPW / 2; ++m) { SGR_FENCE2(P.lpp[m]); }
         if (HAS_RENDER) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) SGR_FENCE2(gds[c]);
-          if (ORTHO) { SGR_FENCE2(oq.vB); SGR_FENCE2(oq.ff); SGR_FENCE2(orow.n2c); SGR_FENCE2(orow.cvc); }
+          if (ORTHO) {
+            SGR_FENCE2(oq.vB); SGR_FENCE2(oq.ff);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) { SGR_FENCE2(orow[r].n2c); SGR_FENCE2(orow[r].cvc); }
+          }
         }
 #endif
         // (round 4, measured and not adopted: this pair's table entries requested one iteration ahead, and the cotangent pairs read behind
@@ -1128,68 +1211,99 @@ __global__ __launch_bounds__(kWave, 2) void sg_bwd_pk_kernel(const Args a) {
         // on one box, profiles/r04d_variants.txt: at two waves per SIMD the other wave already covers the ~150 cycles)
         const f32x4 cs = cpt[aoff + ap];
         const f32x2 ca = {cs[0], cs[1]}, sa = {cs[2], cs[3]};
-        f32x2 g[2][3];            // [sign][colour], the azimuth pair (2 ap, 2 ap + 1) of this virtual row
+        f32x2 g[NR][2][3];        // [row][sign][colour], the azimuth pair (2 ap, 2 ap + 1)
         if (HAS_GENV && !(SGR_ABLATE & 2)) {
-          tile32_read_two_pairs2(cur, pl, ap * 2, HALF + ap * 2, g[0], g[1]);
+          if (NR == 1) tile32_read_two_pairs2(cur, pl, ap * 2, HALF + ap * 2, g[0][0], g[0][1]);
+          else tile32_read_four_pairs2(cur, pl, a2 * 2, g[0][0], g[0][1], g[NR - 1][0], g[NR - 1][1]);
         } else if (HAS_GENV) {      // ablation: cotangents that are neither loaded nor constant-foldable
 #pragma unroll
-          for (int c = 0; c < 3; ++c) g[0][c] = g[1][c] = splat2(1e-3f * (float)(ap + c + lane));
+          for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[r][0][c] = g[r][1][c] = splat2(1e-3f * (float)(ap + c + lane));
           (void)cur;
         } else {
 #pragma unroll
-          for (int c = 0; c < 3; ++c) g[0][c] = g[1][c] = splat2(0.f);
+          for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[r][0][c] = g[r][1][c] = splat2(0.f);
         }
         if (HAS_RENDER) {
           // the render term of the half row this half-wave owns, then both halves' terms to all lanes
-          const f32x2 Pv = pfma(SGR_HI(oq.vB), sa, SGR_LO(oq.vB) * ca);
-          f32x2 wt, sp;
-          shade_pair<ORTHO>(q, oq, rc, orow, own, ca, sa, Pv, xt, (aoff + ap) * 2, wt, sp);
-          // what travels between the halves is the specular term alone (2 swaps; the weight as well for degenerate frames,
-          // where it depends on the direction): the cotangent  wt (gD A/pi + gS spec)  of both half rows is then formed by
-          // every lane -- 12 packed instructions either way, four (two) v_permlane32_swap fewer than trading the six products
-          float dx = sp.x, sx = sp.x, dy = sp.y, sy = sp.y;
-          swap32(dx, sx);
-          swap32(dy, sy);
-          const f32x2 sp1 = {dx, dy}, sp0 = {sx, sy};      // half row 1: evaluated by lanes 0..31; half row 0: by lanes 32..63
-          f32x2 wt1 = wt, wt0 = wt;
-          if (!ORTHO) {
-            float ux = wt.x, vx = wt.x, uy = wt.y, vy = wt.y;
-            swap32(ux, vx);
-            swap32(uy, vy);
-            wt1 = f32x2{ux, uy}; wt0 = f32x2{vx, vy};
-          }
+          const f32x2 Pv = pfma(SGR_HI(oq.vB), sa, SGR_LO(oq.vB) * ca);      // the same for every row of the pass
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            g[1][c] = pfma(wt1, pfma(SGR_HI(gds[c]), sp1, SGR_LO(gds[c])), g[1][c]);
-            g[0][c] = pfma(wt0, pfma(SGR_HI(gds[c]), sp0, SGR_LO(gds[c])), g[0][c]);
+          for (int r = 0; r < NR; ++r) {
+            f32x2 wt, sp;
+            shade_pair<ORTHO>(q, oq, rc[r], orow[r], own, ca, sa, Pv, xt, (aoff + ap) * 2, wt, sp);
+            // what travels between the halves is the specular term alone (2 swaps; the weight as well for degenerate frames,
+            // where it depends on the direction): the cotangent  wt (gD A/pi + gS spec)  of both half rows is then formed by
+            // every lane -- 12 packed instructions either way, four (two) v_permlane32_swap fewer than trading the six products
+            float dx = sp.x, sx = sp.x, dy = sp.y, sy = sp.y;
+            swap32(dx, sx);
+            swap32(dy, sy);
+            const f32x2 sp1 = {dx, dy}, sp0 = {sx, sy};      // half row 1: evaluated by lanes 0..31; half row 0: by lanes 32..63
+            f32x2 wt1 = wt, wt0 = wt;
+            if (!ORTHO) {
+              float ux = wt.x, vx = wt.x, uy = wt.y, vy = wt.y;
+              swap32(ux, vx);
+              swap32(uy, vy);
+              wt1 = f32x2{ux, uy}; wt0 = f32x2{vx, vy};
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              g[r][1][c] = pfma(wt1, pfma(SGR_HI(gds[c]), sp1, SGR_LO(gds[c])), g[r][1][c]);
+              g[r][0][c] = pfma(wt0, pfma(SGR_HI(gds[c]), sp0, SGR_LO(gds[c])), g[r][0][c]);
+            }
           }
         }
-        const f32x2 srv = splat2(sr);
-        const f32x2 sca = srv * ca, ssa = srv * sa;
+        // one row: s_e ca and s_e sa once per azimuth pair (2 + 2 per lobe); two rows: the rows' s_e (T+ - T-) are added first and
+        // meet ca and sa once (4 per lobe for both rows, and no s_e ca / s_e sa pairs to keep)
+        f32x2 srv[NR], sca = splat2(0.f), ssa = splat2(0.f);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) srv[r] = splat2(sr[r]);
+        if (NR == 1) { sca = srv[0] * ca; ssa = srv[0] * sa; }
 #pragma unroll
         for (int k = 0; k < KPW; ++k) {
-          const f32x2 cz = half_of(czr[k / 2], k & 1), w2 = half_of(P.w2p[k / 2], k & 1);
-          const f32x2 u = pfma(SGR_HI(P.axy[k]), sa, SGR_LO(P.axy[k]) * ca);
-          const f32x2 tp = pfma(srv, u, cz), tm = pfma(-srv, u, cz);      // lp t
-          const f32x2 ep = {fexp2(tp.x), fexp2(tp.y)}, em = {fexp2(tm.x), fexp2(tm.y)};
-          gw0[k] = pfma(g[0][0], ep, gw0[k]); gw1[k] = pfma(g[0][1], ep, gw1[k]); gw2[k] = pfma(g[0][2], ep, gw2[k]);
-          gw0[k] = pfma(g[1][0], em, gw0[k]); gw1[k] = pfma(g[1][1], em, gw1[k]); gw2[k] = pfma(g[1][2], em, gw2[k]);
-          // T+- = (g . w) E+-  enter through their sum and difference alone (no sum T t: see the epilogue) -- 3 packed instructions
-          const f32x2 Sp = pfma(g[0][2], w2, pfma(g[0][1], SGR_HI(P.w01[k]), g[0][0] * SGR_LO(P.w01[k])));
-          const f32x2 Sm = pfma(g[1][2], w2, pfma(g[1][1], SGR_HI(P.w01[k]), g[1][0] * SGR_LO(P.w01[k])));
-          const f32x2 Tm = Sm * em;
-          const f32x2 Ts = pfma(Sp, ep, Tm), Td = pfma(Sp, ep, -Tm);
-          gz[k] = pfma(splat2(cr), Ts, gz[k]);
-          gx[k] = pfma(sca, Td, gx[k]);
-          gy[k] = pfma(ssa, Td, gy[k]);
+          const f32x2 w2 = half_of(P.w2p[k / 2], k & 1);
+          const f32x2 u = pfma(SGR_HI(P.axy[k]), sa, SGR_LO(P.axy[k]) * ca);      // the same for every row of the pass
+          f32x2 sTd = splat2(0.f);
+#pragma unroll
+          for (int r = 0; r < NR; ++r) {
+            const f32x2 cz = half_of(czr[r][k / 2], k & 1);
+            const f32x2 tp = pfma(srv[r], u, cz), tm = pfma(-srv[r], u, cz);      // lp t
+            const f32x2 ep = {fexp2(tp.x), fexp2(tp.y)}, em = {fexp2(tm.x), fexp2(tm.y)};
+            gw0[k] = pfma(g[r][0][0], ep, gw0[k]); gw1[k] = pfma(g[r][0][1], ep, gw1[k]); gw2[k] = pfma(g[r][0][2], ep, gw2[k]);
+            gw0[k] = pfma(g[r][1][0], em, gw0[k]); gw1[k] = pfma(g[r][1][1], em, gw1[k]); gw2[k] = pfma(g[r][1][2], em, gw2[k]);
+            // T+- = (g . w) E+-  enter through their sum and difference alone (no sum T t: see the epilogue) -- 3 packed instructions
+            const f32x2 Sp = pfma(g[r][0][2], w2, pfma(g[r][0][1], SGR_HI(P.w01[k]), g[r][0][0] * SGR_LO(P.w01[k])));
+            const f32x2 Sm = pfma(g[r][1][2], w2, pfma(g[r][1][1], SGR_HI(P.w01[k]), g[r][1][0] * SGR_LO(P.w01[k])));
+            const f32x2 Tm = Sm * em;
+            const f32x2 Ts = pfma(Sp, ep, Tm), Td = pfma(Sp, ep, -Tm);
+            gz[k] = pfma(splat2(cr[r]), Ts, gz[k]);
+            if (NR == 1) {
+              gx[k] = pfma(sca, Td, gx[k]);
+              gy[k] = pfma(ssa, Td, gy[k]);
+            } else {
+              sTd = r == 0 ? srv[r] * Td : pfma(srv[r], Td, sTd);
+            }
+          }
+          if (NR > 1) {
+            gx[k] = pfma(ca, sTd, gx[k]);
+            gy[k] = pfma(sa, sTd, gy[k]);
+          }
         }
       }
-      if (HAS_GENV && !(SGR_ABLATE & 1) && (vr & 1) == 0) {
-        // row vr is consumed: its buffer and the one of row vr-1 are free -> request rows vr+2 and vr+3 back to back
-        if (vr + 2 < nvr) tile32_dma_issue_vrow<SGR_PK_BWD_AUX, EW>(tile + ((vr + 2) % 3) * kT32Floats, gimg, x.p0, RC, a.J, vr + 2, lane);
-        if (vr + 3 < nvr) tile32_dma_issue_vrow<SGR_PK_BWD_AUX, EW>(tile + ((vr + 3) % 3) * kT32Floats, gimg, x.p0, RC, a.J, vr + 3, lane);
+      if (HAS_GENV && !(SGR_ABLATE & 1) && (u & 1) == 0) {
+        // unit u is consumed: its buffer and the one of unit u-1 are free -> request units u+2 and u+3 back to back
+        if (u + 2 < nvr) issue_unit(u + 2);
+        if (u + 3 < nvr) issue_unit(u + 3);
       }
     }
+  };
+  auto row_loop = [&](auto ortho_c) {
+    int u = 0;
+    if constexpr (PAIR)
+      for (; u < npu; u += 2) pass(ortho_c, std::integral_constant<int, 2>{}, u);
+    for (; u < nvr; ++u) pass(ortho_c, std::integral_constant<int, 1>{}, u);
   };
   if (ortho) row_loop(std::true_type{}); else row_loop(std::false_type{});
 
