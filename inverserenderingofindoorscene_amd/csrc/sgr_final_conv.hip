@@ -341,11 +341,11 @@ extern "C" int sgr_final_conv_fwd(const float* x, const float* weight, const flo
   const dim3 grid(tilesX * tilesY, B), block(kFcThreads);
   const size_t lds = fc_lds_bytes(C, 2 * kFcTile);
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = W % 4 == 0 && aligned16({out});
-#define FC_FWD(P, V) hipLaunchKernelGGL((fc_fwd_kernel<P, V>), grid, block, lds, st, x, xs, weight, bias, gn_weight, gn_bias, stats, out, C, cpg, H, W, tilesX)
-  if (stats) { if (vec) FC_FWD(true, true); else FC_FWD(true, false); }
-  else { if (vec) FC_FWD(false, true); else FC_FWD(false, false); }
-#undef FC_FWD
+  with_flag(stats != nullptr, [&](auto PROLOGUE) {
+    with_flag(W % 4 == 0 && aligned16({out}), [&](auto VEC) {
+      hipLaunchKernelGGL((fc_fwd_kernel<PROLOGUE(), VEC()>), grid, block, lds, st, x, xs, weight, bias, gn_weight, gn_bias, stats, out, C, cpg, H, W, tilesX);
+    });
+  });
   return sgr_check((int)hipGetLastError(), "sgr_final_conv_fwd");
 }
 
@@ -366,10 +366,9 @@ extern "C" int sgr_final_conv_bwd(const float* g, const float* x, const float* w
     const int tilesX = (W + kFcTW - 1) / kFcTW, tilesY = (H + kFcTHb - 1) / kFcTHb;
     const dim3 grid(tilesX * tilesY, B), block(kFcThreads);
     const size_t lds = fc_lds_bytes(C, kFcOut * kFcTileB);
-    if (W % 4 == 0 && aligned16({dy}))
-      hipLaunchKernelGGL(fc_bwd_data_kernel<true>, grid, block, lds, st, g, weight, dy, C, H, W, tilesX);
-    else
-      hipLaunchKernelGGL(fc_bwd_data_kernel<false>, grid, block, lds, st, g, weight, dy, C, H, W, tilesX);
+    with_flag(W % 4 == 0 && aligned16({dy}), [&](auto VEC) {
+      hipLaunchKernelGGL(fc_bwd_data_kernel<VEC()>, grid, block, lds, st, g, weight, dy, C, H, W, tilesX);
+    });
   }
   if (dweight || dbias) {
     const int S = fc_w_slices(H, W), want_w = dweight != nullptr, cpg = (want_w && stats) ? C / G : C;
@@ -377,10 +376,9 @@ extern "C" int sgr_final_conv_bwd(const float* g, const float* x, const float* w
     float* partial_b = dbias ? workspace + (long long)B * C * S * kFcWPitch : nullptr;
     const FcStrides xs = want_w ? FcStrides{x_strides[0], x_strides[1], x_strides[2], x_strides[3]} : FcStrides{0, 0, 0, 0};
     const dim3 grid(S, want_w ? C : 1, B);
-    if (want_w && stats)
-      hipLaunchKernelGGL(fc_bwd_w_kernel<true>, grid, dim3(kFcThreads), 0, st, g, x, xs, gn_weight, gn_bias, stats, partial_w, partial_b, C, cpg, H, W, want_w);
-    else
-      hipLaunchKernelGGL(fc_bwd_w_kernel<false>, grid, dim3(kFcThreads), 0, st, g, x, xs, gn_weight, gn_bias, stats, partial_w, partial_b, C, cpg, H, W, want_w);
+    with_flag(want_w && stats, [&](auto PROLOGUE) {
+      hipLaunchKernelGGL(fc_bwd_w_kernel<PROLOGUE()>, grid, dim3(kFcThreads), 0, st, g, x, xs, gn_weight, gn_bias, stats, partial_w, partial_b, C, cpg, H, W, want_w);
+    });
     const int nw = want_w ? kFcOut * C * 9 : 0;
     hipLaunchKernelGGL(fc_bwd_fold_kernel, dim3(nw + (dbias ? 3 : 0)), dim3(64), 0, st, partial_w, partial_b, dweight, dbias, B, C, S, nw);
   }

@@ -745,6 +745,8 @@ __global__ __launch_bounds__(kGThreads) void gn_rs_bwd_pass1_kernel(const float*
   gn_rs_bwd_pass1_body<FC>(a, x, xs, weight, bias, stats, dy, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw, blockIdx.y, blockIdx.z);
 }
 
+// ---- host side: what stands between the C entry points and hipLaunchKernelGGL, each refusal sequence and each shared launch once ------------
+
 // the planes of t are rows of W consecutive elements, H W % 4 == 0, and every plane starts on the boundary of a run of four (16 bytes of
 // fp32, 8 of bf16)
 template <typename T>
@@ -755,18 +757,82 @@ static bool g_plane_vec(const T* t, const GnStrides& s, int H, int W) {
 static bool g_plane_fits(const long long* s, int H, int W) {
   return s[2] >= 0 && s[3] >= 0 && (long long)(H - 1) * s[2] + (long long)(W - 1) * s[3] < (1ll << 31);
 }
+// the four strides of the C ABI as the kernels take them; nullptr (a tensor nobody reads) gives zeros
+static GnStrides g_strides(const long long* s) { return s ? GnStrides{s[0], s[1], s[2], s[3]} : GnStrides{0, 0, 0, 0}; }
 static int g_rounds_grid(long long items) { return (int)((items + (long long)kGThreads * kGRounds - 1) / ((long long)kGThreads * kGRounds)); }
 // slices of a plane in backward pass 1
 static int g_bwd_slices(int H, int W) { return g_rounds_grid((long long)H * ((W + 1) / 2)); }
+// slices of a plane in the resize backward's gather: one source pixel per thread and round
+static int rs_bwd_slices(int H, int W) { return g_rounds_grid((long long)H * W); }
+static bool rs_domain(int H, int W, int Hs, int Ws) { return Hs >= H && Hs <= 2 * H && Ws >= W && Ws <= 2 * W; }
 
 // floats of the group coefficients in the backward workspace, a multiple of four: what follows keeps the 16-byte alignment
 static long long g_coef_floats(int B, int G) { return (2ll * B * G + 3) / 4 * 4; }
 
+// The refusals.  Every macro names the entry point's own arguments; the order inside a macro and of the macros in an entry point is the
+// order of the checks, so it decides which message wins when two things are wrong.
 #define GN_CHECK_SIZES(who)                                                                              \
   SGR_REQUIRE(B > 0 && C > 0 && G > 0 && H > 0 && W > 0 && Cs >= 0, who ": non-positive size");          \
   SGR_REQUIRE(C % G == 0, who ": C is not a multiple of num_groups");                                    \
   SGR_SUPPORTED(B <= 65535 && C + Cs <= 65535, who ": B or C + Cs > 65535");                             \
   SGR_SUPPORTED((long long)H * W < (1ll << 26), who ": H * W out of range")
+// the resize forms' target size, after the sizes of the single (GN_CHECK_SIZES) or the sibling form (SIB_CHECK_SIZES)
+#define RS_CHECK_TARGET(who)                                                                                             \
+  SGR_REQUIRE(Hs > 0 && Ws > 0, who ": non-positive size");                                                              \
+  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), who ": outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");            \
+  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), who ": Hs * Ws out of range")
+#define RS_CHECK_SIZES(who) \
+  GN_CHECK_SIZES(who);      \
+  RS_CHECK_TARGET(who)
+// every forward after its NULL checks: SIZES is the family's *_CHECK_SIZES, strides_fit its test of the plane strides
+#define GN_CHECK_FWD(who, SIZES, strides_fit)                                               \
+  SIZES(who);                                                                               \
+  SGR_REQUIRE(eps > 0.0f, who ": eps must be positive");                                    \
+  SGR_SUPPORTED(strides_fit, who ": negative or out-of-range plane strides");               \
+  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, who ": the workspace must be 8-byte aligned")
+// the single operators' forward; the skip's planes are SH x SW
+#define GN_CHECK_SINGLE_FWD(who, SIZES, SH, SW)                                                                                      \
+  SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, who ": NULL tensor");                                   \
+  SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), who ": skip and its channel count do not agree");           \
+  GN_CHECK_FWD(who, SIZES, g_plane_fits(x_strides, H, W) && (!skip || g_plane_fits(skip_strides, SH, SW)))
+// the single operators' backward; side = dx || dweight || dbias, anything behind the normalisation
+#define GN_CHECK_SINGLE_BWD(who, SIZES)                                                                           \
+  SGR_REQUIRE(g, who ": NULL cotangent");                                                                         \
+  SGR_REQUIRE(dx || dweight || dbias || dskip, who ": no gradient requested");                                    \
+  SGR_REQUIRE(!side || (x && weight && bias && stats && workspace && x_strides), who ": NULL tensor");            \
+  SGR_REQUIRE(!dskip || Cs > 0, who ": dskip requested without skip channels");                                   \
+  SIZES(who);                                                                                                     \
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, who ": the workspace must be 8-byte aligned");            \
+  SGR_SUPPORTED(!side || g_plane_fits(x_strides, H, W), who ": negative or out-of-range plane strides")
+
+// The forward's first launch: the (sum, sum of squares) partials of every (b, g), gn_slices(n) per group of n elements.  Small groups
+// take one wave per workgroup.
+static dim3 g_moments_block(long long n) { return dim3(n <= 2048 ? 64 : kGThreads); }
+template <typename T>
+static void launch_moments(const T* x, const GnStrides& xs, double* partials, int B, int G, int cpg, int H, int W, hipStream_t st) {
+  const int HW = H * W;
+  const long long n = (long long)cpg * HW;
+  with_flag(g_plane_vec(x, xs, H, W), [&](auto VEC) {
+    hipLaunchKernelGGL((gn_moments_kernel<VEC(), T>), dim3(gn_slices(n), G, B), g_moments_block(n), 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  });
+}
+// The backward's fold: one wave per (b, g), and one per channel where dweight or dbias is wanted.
+static void launch_fold(const double* partials, const float* weight, float* coef, float* dweight, float* dbias, int B, int C, int cpg, int HW, int P,
+                        hipStream_t st) {
+  const int jobs = B * (C / cpg) + ((dweight || dbias) ? C : 0);
+  hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(jobs), dim3(64), 0, st, partials, weight, coef, dweight, dbias, B, C, cpg, P, (double)cpg * HW);
+}
+// Pass 2 from d: pass 1's fp32 `dy` (MASK = false, TD = float) or the cotangent itself (MASK = true, TD = T).  Runs of four where the
+// planes of x, dx and d all allow them.
+template <bool MASK, typename T, typename TD>
+static void launch_pass2(const TD* d, const T* x, const GnStrides& xs, const float* weight, const float* bias, const float* stats, const float* coef, T* dx,
+                         int B, int C, int cpg, int H, int W, hipStream_t st) {
+  const int HW = H * W;
+  const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C, B);
+  with_flag(g_plane_vec(x, xs, H, W) && aligned_run<T>({dx}) && aligned_run<TD>({d}), [&](auto VEC) {
+    hipLaunchKernelGGL((gn_bwd_pass2_kernel<VEC(), MASK, T, TD>), grid, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
+  });
+}
 
 }  // namespace sgr
 
@@ -785,37 +851,22 @@ extern "C" long long sgr_gn_stage_workspace_floats(int B, int C, int G, int H, i
 template <typename T>
 static int gn_stage_fwd_t(const T* x, const float* weight, const float* bias, const T* skip, T* out, float* stats, float* workspace, int B, int C, int G, int Cs,
                           int H, int W, const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
-  SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, "sgr_gn_stage_fwd: NULL tensor");
-  SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), "sgr_gn_stage_fwd: skip and its channel count do not agree");
-  GN_CHECK_SIZES("sgr_gn_stage_fwd");
-  SGR_REQUIRE(eps > 0.0f, "sgr_gn_stage_fwd: eps must be positive");
-  SGR_SUPPORTED(g_plane_fits(x_strides, H, W) && (!skip || g_plane_fits(skip_strides, H, W)), "sgr_gn_stage_fwd: negative or out-of-range plane strides");
-  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_fwd: the workspace must be 8-byte aligned");
-  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
-  const GnStrides ss = skip ? GnStrides{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]} : GnStrides{0, 0, 0, 0};
-  const int cpg = C / G, HW = H * W;
-  const long long n = (long long)cpg * HW;
-  const int S = gn_slices(n);
+  GN_CHECK_SINGLE_FWD("sgr_gn_stage_fwd", GN_CHECK_SIZES, H, W);
+  const GnStrides xs = g_strides(x_strides), ss = g_strides(skip ? skip_strides : nullptr);
+  const int cpg = C / G, HW = H * W, S = gn_slices((long long)cpg * HW);
   double* partials = reinterpret_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  const bool xvec = g_plane_vec(x, xs, H, W);
-  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
-  if (xvec)
-    hipLaunchKernelGGL((gn_moments_kernel<true, T>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
-  else
-    hipLaunchKernelGGL((gn_moments_kernel<false, T>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
+  launch_moments(x, xs, partials, B, G, cpg, H, W, st);
   if (!skip) {
     const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-    if (xvec && aligned_run<T>({out}))
-      hipLaunchKernelGGL((gn_apply_plain_kernel<true, T>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
-    else
-      hipLaunchKernelGGL((gn_apply_plain_kernel<false, T>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+    with_flag(g_plane_vec(x, xs, H, W) && aligned_run<T>({out}), [&](auto VEC) {
+      hipLaunchKernelGGL((gn_apply_plain_kernel<VEC(), T>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, W, HW, S, eps);
+    });
   } else {
     const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C + Cs, B);
-    if (W % 2 == 0 && aligned_run<T>({out}))
-      hipLaunchKernelGGL((gn_apply_up_kernel<true, T>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
-    else
-      hipLaunchKernelGGL((gn_apply_up_kernel<false, T>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+    with_flag(W % 2 == 0 && aligned_run<T>({out}), [&](auto VEC) {
+      hipLaunchKernelGGL((gn_apply_up_kernel<VEC(), T>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, S, eps);
+    });
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_fwd");
 }
@@ -823,17 +874,11 @@ static int gn_stage_fwd_t(const T* x, const float* weight, const float* bias, co
 template <typename T>
 static int gn_stage_bwd_t(const T* g, const T* x, const float* weight, const float* bias, const float* stats, T* dx, float* dweight, float* dbias, T* dskip,
                           float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, void* stream) {
-  SGR_REQUIRE(g, "sgr_gn_stage_bwd: NULL cotangent");
-  SGR_REQUIRE(dx || dweight || dbias || dskip, "sgr_gn_stage_bwd: no gradient requested");
-  const bool side = dx || dweight || dbias;      // anything behind the normalisation
-  SGR_REQUIRE(!side || (x && weight && bias && stats && workspace && x_strides), "sgr_gn_stage_bwd: NULL tensor");
-  SGR_REQUIRE(!dskip || Cs > 0, "sgr_gn_stage_bwd: dskip requested without skip channels");
-  GN_CHECK_SIZES("sgr_gn_stage_bwd");
-  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_bwd: the workspace must be 8-byte aligned");
-  SGR_SUPPORTED(!side || g_plane_fits(x_strides, H, W), "sgr_gn_stage_bwd: negative or out-of-range plane strides");
+  const bool side = dx || dweight || dbias;
+  GN_CHECK_SINGLE_BWD("sgr_gn_stage_bwd", GN_CHECK_SIZES);
   const bool up = Cs > 0;
   const int cpg = C / G, HW = H * W, P = g_bwd_slices(H, W);
-  const GnStrides xs = side ? GnStrides{x_strides[0], x_strides[1], x_strides[2], x_strides[3]} : GnStrides{0, 0, 0, 0};
+  const GnStrides xs = g_strides(side ? x_strides : nullptr);
   hipStream_t st = (hipStream_t)stream;
   double* partials = reinterpret_cast<double*>(workspace);
   float* coef = side ? workspace + 4ll * B * C * P : nullptr;
@@ -841,29 +886,16 @@ static int gn_stage_bwd_t(const T* g, const T* x, const float* weight, const flo
   // pass 1: the channels somebody wants
   const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
   const dim3 grid1(P, c_end - c_begin, B);
-  if (up) {
-    if (W % 2 == 0 && aligned_run<T>({g}))
-      hipLaunchKernelGGL((gn_bwd_pass1_kernel<true, true, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
-    else
-      hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, true, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
-  } else {
-    hipLaunchKernelGGL((gn_bwd_pass1_kernel<false, false, T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W, c_begin);
-  }
-  if (side) {
-    const int jobs = B * G + ((dweight || dbias) ? C : 0);
-    hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(jobs), dim3(64), 0, st, partials, weight, coef, dweight, dbias, B, C, cpg, P, (double)cpg * HW);
-  }
+  auto pass1 = [&](auto VEC, auto UP) {
+    hipLaunchKernelGGL((gn_bwd_pass1_kernel<VEC(), UP(), T>), grid1, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, dy, dskip, partials, C, Cs, cpg, H, W,
+                       c_begin);
+  };
+  if (up) with_flag(W % 2 == 0 && aligned_run<T>({g}), [&](auto VEC) { pass1(VEC, std::true_type{}); });
+  else pass1(std::false_type{}, std::false_type{});
+  if (side) launch_fold(partials, weight, coef, dweight, dbias, B, C, cpg, HW, P, st);
   if (dx) {
-    const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-    const bool xvec = g_plane_vec(x, xs, H, W) && aligned_run<T>({dx});
-    if (up) {      // from pass 1's fp32 `dy`
-      const float* d = dy;
-      if (xvec && aligned16({d})) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false, T, float>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false, T, float>), grid2, dim3(kGThreads), 0, st, d, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-    } else {       // from the cotangent itself
-      if (xvec && aligned_run<T>({g})) hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, true, T, T>), grid2, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-      else hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, true, T, T>), grid2, dim3(kGThreads), 0, st, g, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-    }
+    if (up) launch_pass2<false, T, float>(dy, x, xs, weight, bias, stats, coef, dx, B, C, cpg, H, W, st);
+    else launch_pass2<true, T, T>(g, x, xs, weight, bias, stats, coef, dx, B, C, cpg, H, W, st);
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_bwd");
 }
@@ -894,18 +926,6 @@ extern "C" int sgr_gn_stage_bwd_bf16(const unsigned short* g, const unsigned sho
 
 // ---- resize-to-skip entry points ------------------------------------------------------------------------------------------------------------
 
-namespace sgr {
-static bool rs_domain(int H, int W, int Hs, int Ws) { return Hs >= H && Hs <= 2 * H && Ws >= W && Ws <= 2 * W; }
-// slices of a plane in the resize backward's gather: one source pixel per thread and round
-static int rs_bwd_slices(int H, int W) { return g_rounds_grid((long long)H * W); }
-
-#define RS_CHECK_SIZES(who)                                                                                              \
-  GN_CHECK_SIZES(who);                                                                                                   \
-  SGR_REQUIRE(Hs > 0 && Ws > 0, who ": non-positive size");                                                              \
-  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), who ": outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");            \
-  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), who ": Hs * Ws out of range")
-}  // namespace sgr
-
 extern "C" long long sgr_gn_resize_workspace_floats(int B, int C, int G, int H, int W, int Hs, int Ws, int upcat, int backward) {
   if (!(B > 0 && C > 0 && G > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0) || C % G != 0 || !rs_domain(H, W, Hs, Ws)) return 0;
   const long long HW = (long long)H * W;
@@ -917,59 +937,38 @@ extern "C" long long sgr_gn_resize_workspace_floats(int B, int C, int G, int H, 
 extern "C" int sgr_gn_resize_fwd(const float* x, const float* weight, const float* bias, const float* skip, float* out, float* stats, float* workspace,
                                  int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides, const long long* skip_strides,
                                  float eps, void* stream) {
-  SGR_REQUIRE(x && weight && bias && out && stats && workspace && x_strides, "sgr_gn_resize_fwd: NULL tensor");
-  SGR_REQUIRE((Cs == 0) == (skip == nullptr) && (!skip || skip_strides), "sgr_gn_resize_fwd: skip and its channel count do not agree");
-  RS_CHECK_SIZES("sgr_gn_resize_fwd");
-  SGR_REQUIRE(eps > 0.0f, "sgr_gn_resize_fwd: eps must be positive");
-  SGR_SUPPORTED(g_plane_fits(x_strides, H, W) && (!skip || g_plane_fits(skip_strides, Hs, Ws)), "sgr_gn_resize_fwd: negative or out-of-range plane strides");
-  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_fwd: the workspace must be 8-byte aligned");
-  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
-  const GnStrides ss = skip ? GnStrides{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]} : GnStrides{0, 0, 0, 0};
-  const int cpg = C / G, HW = H * W;
-  const long long n = (long long)cpg * HW;
-  const int S = gn_slices(n);
+  GN_CHECK_SINGLE_FWD("sgr_gn_resize_fwd", RS_CHECK_SIZES, Hs, Ws);
+  const GnStrides xs = g_strides(x_strides), ss = g_strides(skip ? skip_strides : nullptr);
+  const int cpg = C / G, S = gn_slices((long long)cpg * H * W);
   const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws;
   double* partials = reinterpret_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
-  if (g_plane_vec(x, xs, H, W))
-    hipLaunchKernelGGL((gn_moments_kernel<true, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
-  else
-    hipLaunchKernelGGL((gn_moments_kernel<false, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
-  const bool samew = W == Ws;
-#define RS_LAUNCH(kernel, vec, grid, ...)                                                                                   \
-  do {                                                                                                                      \
-    if (vec) {                                                                                                              \
-      if (samew) hipLaunchKernelGGL((kernel<true, true>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                       \
-      else hipLaunchKernelGGL((kernel<true, false>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                            \
-    } else {                                                                                                                \
-      if (samew) hipLaunchKernelGGL((kernel<false, true>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                      \
-      else hipLaunchKernelGGL((kernel<false, false>), grid, dim3(kGThreads), 0, st, __VA_ARGS__);                           \
-    }                                                                                                                       \
-  } while (0)
+  launch_moments(x, xs, partials, B, G, cpg, H, W, st);
   if (!skip) {
     const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 3) / 4)), C, B);
-    RS_LAUNCH(gn_apply_rs_kernel, Ws % 4 == 0 && aligned16({out}), grid, x, xs, weight, bias, partials, stats, out, C, cpg, H, W, Hs, Ws, sch, scw, S, eps);
+    with_flag(Ws % 4 == 0 && aligned16({out}), [&](auto VEC) {
+      with_flag(W == Ws, [&](auto SAMEW) {
+        hipLaunchKernelGGL((gn_apply_rs_kernel<VEC(), SAMEW()>), grid, dim3(kGThreads), 0, st, x, xs, weight, bias, partials, stats, out, C, cpg, H, W, Hs, Ws, sch,
+                           scw, S, eps);
+      });
+    });
   } else {
     const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 1) / 2)), C + Cs, B);
-    RS_LAUNCH(gn_apply_rsup_kernel, Ws % 2 == 0 && aligned16({out}), grid, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H, W, Hs, Ws, sch,
-              scw, S, eps);
+    with_flag(Ws % 2 == 0 && aligned16({out}), [&](auto VEC) {
+      with_flag(W == Ws, [&](auto SAMEW) {
+        hipLaunchKernelGGL((gn_apply_rsup_kernel<VEC(), SAMEW()>), grid, dim3(kGThreads), 0, st, x, xs, skip, ss, weight, bias, partials, stats, out, C, Cs, cpg, H,
+                           W, Hs, Ws, sch, scw, S, eps);
+      });
+    });
   }
-#undef RS_LAUNCH
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_fwd");
 }
 
 extern "C" int sgr_gn_resize_bwd(const float* g, const float* x, const float* weight, const float* bias, const float* stats, float* dx, float* dweight,
                                  float* dbias, float* dskip, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
                                  const long long* x_strides, void* stream) {
-  SGR_REQUIRE(g, "sgr_gn_resize_bwd: NULL cotangent");
-  SGR_REQUIRE(dx || dweight || dbias || dskip, "sgr_gn_resize_bwd: no gradient requested");
-  const bool side = dx || dweight || dbias;      // anything behind the normalisation
-  SGR_REQUIRE(!side || (x && weight && bias && stats && workspace && x_strides), "sgr_gn_resize_bwd: NULL tensor");
-  SGR_REQUIRE(!dskip || Cs > 0, "sgr_gn_resize_bwd: dskip requested without skip channels");
-  RS_CHECK_SIZES("sgr_gn_resize_bwd");
-  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_bwd: the workspace must be 8-byte aligned");
-  SGR_SUPPORTED(!side || g_plane_fits(x_strides, H, W), "sgr_gn_resize_bwd: negative or out-of-range plane strides");
+  const bool side = dx || dweight || dbias;
+  GN_CHECK_SINGLE_BWD("sgr_gn_resize_bwd", RS_CHECK_SIZES);
   const bool up = Cs > 0;
   const int cpg = C / G, HW = H * W, P = rs_bwd_slices(H, W);
   hipStream_t st = (hipStream_t)stream;
@@ -980,30 +979,21 @@ extern "C" int sgr_gn_resize_bwd(const float* g, const float* x, const float* we
   if (up) {      // step 1: the upsample's adjoint of the channels somebody wants
     const int c_begin = side ? 0 : C, c_end = dskip ? C + Cs : C;
     const dim3 grid(g_bwd_slices(Hs, Ws), c_end - c_begin, B);
-    if (Ws % 2 == 0 && aligned16({g}))
-      hipLaunchKernelGGL(gn_up_adjoint_kernel<true>, grid, dim3(kGThreads), 0, st, g, da, dskip, C, Cs, Hs, Ws, c_begin);
-    else
-      hipLaunchKernelGGL(gn_up_adjoint_kernel<false>, grid, dim3(kGThreads), 0, st, g, da, dskip, C, Cs, Hs, Ws, c_begin);
+    with_flag(Ws % 2 == 0 && aligned16({g}), [&](auto VEC) {
+      hipLaunchKernelGGL(gn_up_adjoint_kernel<VEC()>, grid, dim3(kGThreads), 0, st, g, da, dskip, C, Cs, Hs, Ws, c_begin);
+    });
   }
   if (side) {
-    const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
+    const GnStrides xs = g_strides(x_strides);
     const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws, inh = (float)Hs / (float)H, inw = (float)Ws / (float)W;
     const float* a = up ? da : g;
     float* dyo = dx ? dy : nullptr;
-    const dim3 grid1(P, C, B);
-    if (W == Ws)
-      hipLaunchKernelGGL(gn_rs_bwd_pass1_kernel<1>, grid1, dim3(kGThreads), 0, st, a, x, xs, weight, bias, stats, dyo, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
-    else
-      hipLaunchKernelGGL(gn_rs_bwd_pass1_kernel<kRsFan>, grid1, dim3(kGThreads), 0, st, a, x, xs, weight, bias, stats, dyo, partials, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
-    const int jobs = B * G + ((dweight || dbias) ? C : 0);
-    hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(jobs), dim3(64), 0, st, partials, weight, coef, dweight, dbias, B, C, cpg, P, (double)cpg * HW);
-    if (dx) {
-      const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C, B);
-      if (g_plane_vec(x, xs, H, W) && aligned16({dy, dx}))
-        hipLaunchKernelGGL((gn_bwd_pass2_kernel<true, false, float, float>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-      else
-        hipLaunchKernelGGL((gn_bwd_pass2_kernel<false, false, float, float>), grid2, dim3(kGThreads), 0, st, dy, x, xs, weight, bias, stats, coef, dx, C, cpg, W, HW);
-    }
+    choose<Int<1>, Int<kRsFan>>(W == Ws, [&](auto FC) {
+      hipLaunchKernelGGL(gn_rs_bwd_pass1_kernel<FC()>, dim3(P, C, B), dim3(kGThreads), 0, st, a, x, xs, weight, bias, stats, dyo, partials, C, cpg, H, W, Hs, Ws, sch,
+                         scw, inh, inw);
+    });
+    launch_fold(partials, weight, coef, dweight, dbias, B, C, cpg, HW, P, st);
+    if (dx) launch_pass2<false, float, float>(dy, x, xs, weight, bias, stats, coef, dx, B, C, cpg, H, W, st);
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_bwd");
 }
@@ -1014,23 +1004,14 @@ extern "C" int sgr_gn_moments(const float* x, float* stats, float* workspace, in
                               void* stream) {
   SGR_REQUIRE(x && stats && workspace && x_strides, "sgr_gn_moments: NULL tensor");
   const int Cs = 0;
-  GN_CHECK_SIZES("sgr_gn_moments");
-  SGR_REQUIRE(eps > 0.0f, "sgr_gn_moments: eps must be positive");
-  SGR_SUPPORTED(g_plane_fits(x_strides, H, W), "sgr_gn_moments: negative or out-of-range plane strides");
-  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_moments: the workspace must be 8-byte aligned");
-  const GnStrides xs{x_strides[0], x_strides[1], x_strides[2], x_strides[3]};
-  const int cpg = C / G, HW = H * W;
-  const long long n = (long long)cpg * HW;
-  const int S = gn_slices(n);
+  GN_CHECK_FWD("sgr_gn_moments", GN_CHECK_SIZES, g_plane_fits(x_strides, H, W));
+  const int cpg = C / G;
+  const long long n = (long long)cpg * H * W;
   double* partials = reinterpret_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   // the launch of sgr_gn_stage_fwd: the same partials, and gn_group_stat folds them to the same bits
-  const dim3 mgrid(S, G, B), mblock(n <= 2048 ? 64 : kGThreads);
-  if (g_plane_vec(x, xs, H, W))
-    hipLaunchKernelGGL((gn_moments_kernel<true, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
-  else
-    hipLaunchKernelGGL((gn_moments_kernel<false, float>), mgrid, mblock, 0, st, x, xs, partials, cpg, W, HW, gn_slice_len(n));
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, st, partials, stats, S, (double)n, eps);
+  launch_moments(x, g_strides(x_strides), partials, B, G, cpg, H, W, st);
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(B * G), dim3(64), 0, st, partials, stats, gn_slices(n), (double)n, eps);
   return sgr_check((int)hipGetLastError(), "sgr_gn_moments");
 }
 
@@ -1192,14 +1173,20 @@ __global__ __launch_bounds__(kGThreads) void gn_sib_rs_bwd_pass1_kernel(SibBwd<f
                            W, Hs, Ws, sch, scw, inh, inw, ch, blockIdx.z);
 }
 
+// ---- host side of the sibling forms -----------------------------------------------------------------------------------------------------------
+
 // a block of the sibling workspace: the single operator's floats, rounded up so that every block starts on 16 bytes
 static long long sib_block(long long single) { return (single + 3) / 4 * 4; }
-
-#define SIB_CHECK_SIZES(who)                                                                                     \
-  SGR_REQUIRE(D >= 1 && D <= kGSiblings, who ": the number of siblings must be 1 .. 8");                          \
-  GN_CHECK_SIZES(who);                                                                                           \
-  SGR_REQUIRE(Cs > 0, who ": the sibling forms need a skip");                                                     \
-  SGR_SUPPORTED((long long)C * D + Cs <= 65535 && (long long)G * D <= 65535, who ": D * C + Cs or D * G > 65535")
+// The backward workspace: D blocks of partials, coefficients, dy and (resize form: da_floats of) da, each laid out as the single operator's.
+static SibWs sib_ws(float* workspace, int B, int C, int G, int HW, int P, long long da_floats) {
+  SibWs ws;
+  ws.base = workspace;
+  ws.coef = 4ll * B * C * P;
+  ws.dy = ws.coef + g_coef_floats(B, G);
+  ws.da = da_floats ? ws.dy + (long long)B * C * HW : 0;
+  ws.stride = sib_block(ws.dy + (long long)B * C * HW + da_floats);
+  return ws;
+}
 
 template <typename T>
 static bool sib_fwd_table(SibFwd<T>& t, int D, const T* const* xs, const float* const* weights, const float* const* biases, T* const* outs,
@@ -1208,9 +1195,8 @@ static bool sib_fwd_table(SibFwd<T>& t, int D, const T* const* xs, const float* 
   for (int d = 0; d < kGSiblings; ++d) {
     const int e = d < D ? d : 0;      // the unused entries repeat sibling 0: no kernel reads them
     if (!xs[e] || !weights[e] || !biases[e] || !outs[e]) return false;
-    const long long* s = x_strides + 4 * e;
     t.x[d] = xs[e]; t.weight[d] = weights[e]; t.bias[d] = biases[e]; t.out[d] = outs[e];
-    t.xs[d] = GnStrides{s[0], s[1], s[2], s[3]};
+    t.xs[d] = g_strides(x_strides + 4 * e);
     xvec = xvec && g_plane_vec(t.x[d], t.xs[d], H, W);
     ovec = ovec && aligned_run<T>({t.out[d]});
   }
@@ -1220,38 +1206,6 @@ static bool sib_strides_fit(int D, const long long* x_strides, int H, int W) {
   for (int d = 0; d < D; ++d)
     if (!g_plane_fits(x_strides + 4 * d, H, W)) return false;
   return true;
-}
-
-template <typename T>
-static int gn_stage_siblings_fwd_t(int D, const T* const* xs, const float* const* weights, const float* const* biases, const T* skip, T* const* outs, float* stats,
-                                   float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides,
-                                   float eps, void* stream) {
-  SGR_REQUIRE(xs && weights && biases && skip && outs && stats && workspace && x_strides && skip_strides, "sgr_gn_stage_siblings_fwd: NULL tensor");
-  SIB_CHECK_SIZES("sgr_gn_stage_siblings_fwd");
-  SGR_REQUIRE(eps > 0.0f, "sgr_gn_stage_siblings_fwd: eps must be positive");
-  SGR_SUPPORTED(sib_strides_fit(D, x_strides, H, W) && g_plane_fits(skip_strides, H, W), "sgr_gn_stage_siblings_fwd: negative or out-of-range plane strides");
-  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_siblings_fwd: the workspace must be 8-byte aligned");
-  SibFwd<T> t;
-  bool xvec, ovec;
-  SGR_REQUIRE(sib_fwd_table(t, D, xs, weights, biases, outs, x_strides, H, W, xvec, ovec), "sgr_gn_stage_siblings_fwd: NULL tensor of a sibling");
-  const GnStrides ss{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]};
-  const int cpg = C / G, HW = H * W;
-  const long long n = (long long)cpg * HW;
-  const int S = gn_slices(n);
-  const long long stride = 2ll * B * G * S;      // doubles: the single forward's workspace
-  double* partials = reinterpret_cast<double*>(workspace);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 mgrid(S, G * D, B), mblock(n <= 2048 ? 64 : kGThreads);
-  if (xvec)
-    hipLaunchKernelGGL((gn_sib_moments_kernel<true, T>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
-  else
-    hipLaunchKernelGGL((gn_sib_moments_kernel<false, T>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
-  const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C * D + Cs, B);
-  if (W % 2 == 0 && ovec)
-    hipLaunchKernelGGL((gn_sib_apply_up_kernel<true, T>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, S, eps);
-  else
-    hipLaunchKernelGGL((gn_sib_apply_up_kernel<false, T>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, S, eps);
-  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_siblings_fwd");
 }
 
 // The backward's table: a sibling without a cotangent gets no gradient; `any` = some sibling wants dx, dweight or dbias.
@@ -1266,13 +1220,12 @@ static bool sib_bwd_table(SibBwd<T>& t, int D, const T* const* gs, const T* cons
     t.dweight[d] = has && dweights ? dweights[d] : nullptr;
     t.dbias[d] = has && dbiases ? dbiases[d] : nullptr;
     t.x[d] = nullptr; t.weight[d] = nullptr; t.bias[d] = nullptr;
-    t.xs[d] = GnStrides{0, 0, 0, 0};
+    t.xs[d] = g_strides(nullptr);
     anyg = anyg || has;
     if (t.dx[d] || t.dweight[d] || t.dbias[d]) {
       if (!xs || !weights || !biases || !x_strides || !xs[d] || !weights[d] || !biases[d]) return false;
-      const long long* s = x_strides + 4 * d;
       t.x[d] = xs[d]; t.weight[d] = weights[d]; t.bias[d] = biases[d];
-      t.xs[d] = GnStrides{s[0], s[1], s[2], s[3]};
+      t.xs[d] = g_strides(x_strides + 4 * d);
       any = true;
       anyw = anyw || t.dweight[d] || t.dbias[d];
       anydx = anydx || t.dx[d];
@@ -1312,43 +1265,94 @@ static SibBwd<float> sib_fold_table(const SibBwd<T>& t) {
   return f;
 }
 
+// The refusals of the sibling forms, in the order of the single forms' (above) around the two tables.
+#define SIB_CHECK_SIZES(who)                                                                                     \
+  SGR_REQUIRE(D >= 1 && D <= kGSiblings, who ": the number of siblings must be 1 .. 8");                          \
+  GN_CHECK_SIZES(who);                                                                                           \
+  SGR_REQUIRE(Cs > 0, who ": the sibling forms need a skip");                                                     \
+  SGR_SUPPORTED((long long)C * D + Cs <= 65535 && (long long)G * D <= 65535, who ": D * C + Cs or D * G > 65535")
+#define SIB_RS_CHECK_SIZES(who) \
+  SIB_CHECK_SIZES(who);         \
+  RS_CHECK_TARGET(who)
+// the forward: fills the table t and the predicates xvec, ovec of the caller; the skip's planes are SH x SW
+#define SIB_CHECK_FWD(who, SIZES, SH, SW)                                                                                           \
+  SGR_REQUIRE(xs && weights && biases && skip && outs && stats && workspace && x_strides && skip_strides, who ": NULL tensor");     \
+  GN_CHECK_FWD(who, SIZES, sib_strides_fit(D, x_strides, H, W) && g_plane_fits(skip_strides, SH, SW));                              \
+  SGR_REQUIRE(sib_fwd_table(t, D, xs, weights, biases, outs, x_strides, H, W, xvec, ovec), who ": NULL tensor of a sibling")
+// the backward: fills the table t and side, anyg, anyw, anydx of the caller
+#define SIB_CHECK_BWD(who, SIZES)                                                                                                                 \
+  SGR_REQUIRE(gs, who ": NULL cotangent");                                                                                                        \
+  SIZES(who);                                                                                                                                     \
+  SGR_REQUIRE(sib_bwd_table(t, D, gs, xs, weights, biases, dxs, dweights, dbiases, x_strides, side, anyg, anyw, anydx), who ": NULL tensor");     \
+  SGR_REQUIRE(anyg, who ": NULL cotangent");                                                                                                      \
+  SGR_REQUIRE(side || dskip, who ": no gradient requested");                                                                                      \
+  SGR_REQUIRE(!side || (stats && workspace), who ": NULL tensor");                                                                                \
+  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, who ": the workspace must be 8-byte aligned");                                            \
+  SGR_SUPPORTED(sib_bwd_strides_fit(t, D, H, W), who ": negative or out-of-range plane strides")
+
+// launch_moments for D siblings: sibling d's partials start at d * stride doubles, the single forward's workspace
+template <typename T>
+static void launch_sib_moments(const SibFwd<T>& t, bool xvec, double* partials, long long stride, int D, int B, int G, int cpg, int H, int W, hipStream_t st) {
+  const int HW = H * W;
+  const long long n = (long long)cpg * HW;
+  with_flag(xvec, [&](auto VEC) {
+    hipLaunchKernelGGL((gn_sib_moments_kernel<VEC(), T>), dim3(gn_slices(n), G * D, B), g_moments_block(n), 0, st, t, partials, stride, G, cpg, W, HW,
+                       gn_slice_len(n));
+  });
+}
+// launch_fold for D siblings; f is the table or its sib_fold_table
+static void launch_sib_fold(const SibBwd<float>& f, const SibWs& ws, bool anyw, int D, int B, int C, int cpg, int HW, int P, hipStream_t st) {
+  hipLaunchKernelGGL(gn_sib_bwd_fold_kernel, dim3(B * (C / cpg) + (anyw ? C : 0), D), dim3(64), 0, st, f, ws, B, C, cpg, P, (double)cpg * HW);
+}
+// launch_pass2 (from pass 1's `dy`) for D siblings
+template <typename T>
+static void launch_sib_pass2(const SibBwd<T>& t, const float* stats, const SibWs& ws, int D, int B, int C, int cpg, int H, int W, hipStream_t st) {
+  const int HW = H * W;
+  const dim3 grid(g_rounds_grid(((long long)HW + 3) / 4), C * D, B);
+  // sib_dx_vec has HW % 4 == 0: every block's dy is on 16 bytes with the workspace
+  with_flag(sib_dx_vec(t, D, H, W) && aligned16({ws.base}), [&](auto VEC) {
+    hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<VEC(), T>), grid, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
+  });
+}
+
+template <typename T>
+static int gn_stage_siblings_fwd_t(int D, const T* const* xs, const float* const* weights, const float* const* biases, const T* skip, T* const* outs, float* stats,
+                                   float* workspace, int B, int C, int G, int Cs, int H, int W, const long long* x_strides, const long long* skip_strides,
+                                   float eps, void* stream) {
+  SibFwd<T> t;
+  bool xvec, ovec;
+  SIB_CHECK_FWD("sgr_gn_stage_siblings_fwd", SIB_CHECK_SIZES, H, W);
+  const GnStrides ss = g_strides(skip_strides);
+  const int cpg = C / G, S = gn_slices((long long)cpg * H * W);
+  const long long stride = 2ll * B * G * S;      // doubles: the single forward's workspace
+  double* partials = reinterpret_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  launch_sib_moments(t, xvec, partials, stride, D, B, G, cpg, H, W, st);
+  const dim3 grid(g_rounds_grid((long long)H * ((W + 1) / 2)), C * D + Cs, B);
+  with_flag(W % 2 == 0 && ovec, [&](auto VEC) {
+    hipLaunchKernelGGL((gn_sib_apply_up_kernel<VEC(), T>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, S, eps);
+  });
+  return sgr_check((int)hipGetLastError(), "sgr_gn_stage_siblings_fwd");
+}
+
 template <typename T>
 static int gn_stage_siblings_bwd_t(int D, const T* const* gs, const T* const* xs, const float* const* weights, const float* const* biases, const float* stats,
                                    T* const* dxs, float* const* dweights, float* const* dbiases, T* dskip, float* workspace, int B, int C, int G, int Cs, int H,
                                    int W, const long long* x_strides, void* stream) {
-  SGR_REQUIRE(gs, "sgr_gn_stage_siblings_bwd: NULL cotangent");
-  SIB_CHECK_SIZES("sgr_gn_stage_siblings_bwd");
   SibBwd<T> t;
   bool side, anyg, anyw, anydx;
-  SGR_REQUIRE(sib_bwd_table(t, D, gs, xs, weights, biases, dxs, dweights, dbiases, x_strides, side, anyg, anyw, anydx), "sgr_gn_stage_siblings_bwd: NULL tensor");
-  SGR_REQUIRE(anyg, "sgr_gn_stage_siblings_bwd: NULL cotangent");
-  SGR_REQUIRE(side || dskip, "sgr_gn_stage_siblings_bwd: no gradient requested");
-  SGR_REQUIRE(!side || (stats && workspace), "sgr_gn_stage_siblings_bwd: NULL tensor");
-  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_stage_siblings_bwd: the workspace must be 8-byte aligned");
-  SGR_SUPPORTED(sib_bwd_strides_fit(t, D, H, W), "sgr_gn_stage_siblings_bwd: negative or out-of-range plane strides");
+  SIB_CHECK_BWD("sgr_gn_stage_siblings_bwd", SIB_CHECK_SIZES);
   const int cpg = C / G, HW = H * W, P = g_bwd_slices(H, W);
   hipStream_t st = (hipStream_t)stream;
-  SibWs ws;
-  ws.base = workspace;
-  ws.coef = 4ll * B * C * P;
-  ws.dy = ws.coef + g_coef_floats(B, G);
-  ws.da = 0;
-  ws.stride = sib_block(ws.dy + (long long)B * C * HW);
+  const SibWs ws = sib_ws(workspace, B, C, G, HW, P, 0);
   // pass 1: the channels somebody wants
   const int y_begin = side ? 0 : C * D, y_end = dskip ? C * D + Cs : C * D;
   const dim3 grid1(P, y_end - y_begin, B);
-  if (W % 2 == 0 && sib_g_vec(t, D))
-    hipLaunchKernelGGL((gn_sib_bwd_pass1_kernel<true, T>), grid1, dim3(kGThreads), 0, st, t, D, stats, ws, dskip, C, Cs, cpg, H, W, y_begin);
-  else
-    hipLaunchKernelGGL((gn_sib_bwd_pass1_kernel<false, T>), grid1, dim3(kGThreads), 0, st, t, D, stats, ws, dskip, C, Cs, cpg, H, W, y_begin);
-  if (side) hipLaunchKernelGGL(gn_sib_bwd_fold_kernel, dim3(B * G + (anyw ? C : 0), D), dim3(64), 0, st, sib_fold_table(t), ws, B, C, cpg, P, (double)cpg * HW);
-  if (anydx) {
-    const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C * D, B);
-    if (sib_dx_vec(t, D, H, W) && aligned16({workspace}))      // HW % 4 == 0 here: every block's dy is on 16 bytes with the workspace
-      hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<true, T>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
-    else
-      hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<false, T>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
-  }
+  with_flag(W % 2 == 0 && sib_g_vec(t, D), [&](auto VEC) {
+    hipLaunchKernelGGL((gn_sib_bwd_pass1_kernel<VEC(), T>), grid1, dim3(kGThreads), 0, st, t, D, stats, ws, dskip, C, Cs, cpg, H, W, y_begin);
+  });
+  if (side) launch_sib_fold(sib_fold_table(t), ws, anyw, D, B, C, cpg, HW, P, st);
+  if (anydx) launch_sib_pass2(t, stats, ws, D, B, C, cpg, H, W, st);
   return sgr_check((int)hipGetLastError(), "sgr_gn_stage_siblings_bwd");
 }
 
@@ -1393,91 +1397,49 @@ extern "C" long long sgr_gn_resize_siblings_workspace_floats(int D, int B, int C
 extern "C" int sgr_gn_resize_siblings_fwd(int D, const float* const* xs, const float* const* weights, const float* const* biases, const float* skip,
                                           float* const* outs, float* stats, float* workspace, int B, int C, int G, int Cs, int H, int W, int Hs, int Ws,
                                           const long long* x_strides, const long long* skip_strides, float eps, void* stream) {
-  SGR_REQUIRE(xs && weights && biases && skip && outs && stats && workspace && x_strides && skip_strides, "sgr_gn_resize_siblings_fwd: NULL tensor");
-  SIB_CHECK_SIZES("sgr_gn_resize_siblings_fwd");
-  SGR_REQUIRE(Hs > 0 && Ws > 0, "sgr_gn_resize_siblings_fwd: non-positive size");
-  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), "sgr_gn_resize_siblings_fwd: outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");
-  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), "sgr_gn_resize_siblings_fwd: Hs * Ws out of range");
-  SGR_REQUIRE(eps > 0.0f, "sgr_gn_resize_siblings_fwd: eps must be positive");
-  SGR_SUPPORTED(sib_strides_fit(D, x_strides, H, W) && g_plane_fits(skip_strides, Hs, Ws), "sgr_gn_resize_siblings_fwd: negative or out-of-range plane strides");
-  SGR_REQUIRE(((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_siblings_fwd: the workspace must be 8-byte aligned");
   SibFwd<float> t;
   bool xvec, ovec;
-  SGR_REQUIRE(sib_fwd_table(t, D, xs, weights, biases, outs, x_strides, H, W, xvec, ovec), "sgr_gn_resize_siblings_fwd: NULL tensor of a sibling");
-  const GnStrides ss{skip_strides[0], skip_strides[1], skip_strides[2], skip_strides[3]};
-  const int cpg = C / G, HW = H * W;
-  const long long n = (long long)cpg * HW;
-  const int S = gn_slices(n);
+  SIB_CHECK_FWD("sgr_gn_resize_siblings_fwd", SIB_RS_CHECK_SIZES, Hs, Ws);
+  const GnStrides ss = g_strides(skip_strides);
+  const int cpg = C / G, S = gn_slices((long long)cpg * H * W);
   const long long stride = 2ll * B * G * S;
   const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws;
   double* partials = reinterpret_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 mgrid(S, G * D, B), mblock(n <= 2048 ? 64 : kGThreads);
-  if (xvec)
-    hipLaunchKernelGGL((gn_sib_moments_kernel<true, float>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
-  else
-    hipLaunchKernelGGL((gn_sib_moments_kernel<false, float>), mgrid, mblock, 0, st, t, partials, stride, G, cpg, W, HW, gn_slice_len(n));
-  const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 1) / 2)), C * D + Cs, B), block(kGThreads);
-  const bool vec = Ws % 2 == 0 && ovec;
-#define SIB_RS_ARGS t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, Hs, Ws, sch, scw, S, eps
-  if (W == Ws) {
-    if (vec) hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<true, true>), grid, block, 0, st, SIB_RS_ARGS);
-    else hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<false, true>), grid, block, 0, st, SIB_RS_ARGS);
-  } else {
-    if (vec) hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<true, false>), grid, block, 0, st, SIB_RS_ARGS);
-    else hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<false, false>), grid, block, 0, st, SIB_RS_ARGS);
-  }
-#undef SIB_RS_ARGS
+  launch_sib_moments(t, xvec, partials, stride, D, B, G, cpg, H, W, st);
+  const dim3 grid(g_rounds_grid((long long)Hs * ((Ws + 1) / 2)), C * D + Cs, B);
+  with_flag(Ws % 2 == 0 && ovec, [&](auto VEC) {
+    with_flag(W == Ws, [&](auto SAMEW) {
+      hipLaunchKernelGGL((gn_sib_apply_rsup_kernel<VEC(), SAMEW()>), grid, dim3(kGThreads), 0, st, t, D, skip, ss, partials, stride, stats, C, Cs, cpg, H, W, Hs, Ws,
+                         sch, scw, S, eps);
+    });
+  });
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_siblings_fwd");
 }
 
 extern "C" int sgr_gn_resize_siblings_bwd(int D, const float* const* gs, const float* const* xs, const float* const* weights, const float* const* biases,
                                           const float* stats, float* const* dxs, float* const* dweights, float* const* dbiases, float* dskip, float* workspace,
                                           int B, int C, int G, int Cs, int H, int W, int Hs, int Ws, const long long* x_strides, void* stream) {
-  SGR_REQUIRE(gs, "sgr_gn_resize_siblings_bwd: NULL cotangent");
-  SIB_CHECK_SIZES("sgr_gn_resize_siblings_bwd");
-  SGR_REQUIRE(Hs > 0 && Ws > 0, "sgr_gn_resize_siblings_bwd: non-positive size");
-  SGR_SUPPORTED(rs_domain(H, W, Hs, Ws), "sgr_gn_resize_siblings_bwd: outside the resize domain (H <= Hs <= 2H and W <= Ws <= 2W)");
-  SGR_SUPPORTED((long long)Hs * Ws < (1ll << 26), "sgr_gn_resize_siblings_bwd: Hs * Ws out of range");
   SibBwd<float> t;
   bool side, anyg, anyw, anydx;
-  SGR_REQUIRE(sib_bwd_table(t, D, gs, xs, weights, biases, dxs, dweights, dbiases, x_strides, side, anyg, anyw, anydx), "sgr_gn_resize_siblings_bwd: NULL tensor");
-  SGR_REQUIRE(anyg, "sgr_gn_resize_siblings_bwd: NULL cotangent");
-  SGR_REQUIRE(side || dskip, "sgr_gn_resize_siblings_bwd: no gradient requested");
-  SGR_REQUIRE(!side || (stats && workspace), "sgr_gn_resize_siblings_bwd: NULL tensor");
-  SGR_REQUIRE(!side || ((uintptr_t)workspace & 7) == 0, "sgr_gn_resize_siblings_bwd: the workspace must be 8-byte aligned");
-  SGR_SUPPORTED(sib_bwd_strides_fit(t, D, H, W), "sgr_gn_resize_siblings_bwd: negative or out-of-range plane strides");
+  SIB_CHECK_BWD("sgr_gn_resize_siblings_bwd", SIB_RS_CHECK_SIZES);
   const int cpg = C / G, HW = H * W, P = rs_bwd_slices(H, W);
   hipStream_t st = (hipStream_t)stream;
-  SibWs ws;
-  ws.base = workspace;
-  ws.coef = 4ll * B * C * P;
-  ws.dy = ws.coef + g_coef_floats(B, G);
-  ws.da = ws.dy + (long long)B * C * HW;
-  ws.stride = sib_block(ws.da + (long long)B * C * Hs * Ws);
+  const SibWs ws = sib_ws(workspace, B, C, G, HW, P, (long long)B * C * Hs * Ws);
   {      // step 1: the upsample's adjoint of the channels somebody wants
     const int y_begin = side ? 0 : C * D, y_end = dskip ? C * D + Cs : C * D;
     const dim3 grid(g_bwd_slices(Hs, Ws), y_end - y_begin, B);
-    if (Ws % 2 == 0 && sib_g_vec(t, D))
-      hipLaunchKernelGGL(gn_sib_up_adjoint_kernel<true>, grid, dim3(kGThreads), 0, st, t, D, ws, dskip, C, Cs, Hs, Ws, y_begin);
-    else
-      hipLaunchKernelGGL(gn_sib_up_adjoint_kernel<false>, grid, dim3(kGThreads), 0, st, t, D, ws, dskip, C, Cs, Hs, Ws, y_begin);
+    with_flag(Ws % 2 == 0 && sib_g_vec(t, D), [&](auto VEC) {
+      hipLaunchKernelGGL(gn_sib_up_adjoint_kernel<VEC()>, grid, dim3(kGThreads), 0, st, t, D, ws, dskip, C, Cs, Hs, Ws, y_begin);
+    });
   }
   if (side) {
     const float sch = (float)H / (float)Hs, scw = (float)W / (float)Ws, inh = (float)Hs / (float)H, inw = (float)Ws / (float)W;
-    const dim3 grid1(P, C * D, B);
-    if (W == Ws)
-      hipLaunchKernelGGL(gn_sib_rs_bwd_pass1_kernel<1>, grid1, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
-    else
-      hipLaunchKernelGGL(gn_sib_rs_bwd_pass1_kernel<kRsFan>, grid1, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
-    hipLaunchKernelGGL(gn_sib_bwd_fold_kernel, dim3(B * G + (anyw ? C : 0), D), dim3(64), 0, st, t, ws, B, C, cpg, P, (double)cpg * HW);
-    if (anydx) {
-      const dim3 grid2(g_rounds_grid(((long long)HW + 3) / 4), C * D, B);
-      if (sib_dx_vec(t, D, H, W) && aligned16({workspace}))
-        hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<true, float>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
-      else
-        hipLaunchKernelGGL((gn_sib_bwd_pass2_kernel<false, float>), grid2, dim3(kGThreads), 0, st, t, stats, ws, C, cpg, W, HW);
-    }
+    choose<Int<1>, Int<kRsFan>>(W == Ws, [&](auto FC) {
+      hipLaunchKernelGGL(gn_sib_rs_bwd_pass1_kernel<FC()>, dim3(P, C * D, B), dim3(kGThreads), 0, st, t, stats, ws, C, cpg, H, W, Hs, Ws, sch, scw, inh, inw);
+    });
+    launch_sib_fold(t, ws, anyw, D, B, C, cpg, HW, P, st);
+    if (anydx) launch_sib_pass2(t, stats, ws, D, B, C, cpg, H, W, st);
   }
   return sgr_check((int)hipGetLastError(), "sgr_gn_resize_siblings_bwd");
 }

@@ -1,8 +1,10 @@
-// Host-side error plumbing shared by the C-ABI entry points.
+// Host-side plumbing shared by the C-ABI entry points: the error path, and the choice of a kernel's template arguments at run time.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "../../include/sgrender.h"
 
@@ -40,6 +42,16 @@ int render_loss_fwd_launch(const float* diffuse, const float* spec, const float*
       return SGR_ERR_UNSUPPORTED;       \
     }                                   \
   } while (0)
+
+namespace sgr {
+// A run-time value chosen between two template arguments: f is a generic lambda whose parameter carries the constant,
+//   with_flag(vec, [&](auto VEC) { hipLaunchKernelGGL((kernel<VEC()>), ...); });
+// Both branches are instantiated, exactly as by the if / else this replaces.  Two run-time values nest the helper.  with_pool and
+// with_ew (sgr_layer_launch.h) are the render layer's choices, built on `choose`.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class A, class B, class F> static inline auto choose(bool first, F&& f) { return first ? f(A{}) : f(B{}); }
+template <class F> static inline auto with_flag(bool on, F&& f) { return choose<std::true_type, std::false_type>(on, f); }
+}  // namespace sgr
 
 // SGR_GENERIC=1 forces the table-driven generic kernels (tuning / test knob); read once per process
 static inline bool sgr_generic_forced() {

@@ -1,10 +1,9 @@
 // Host side of the render layer: what stands between an extern "C" entry point and hipLaunchKernelGGL, defined once -- the dims
 // block, the pooling and decoder-heads predicates, the half-wave grid and the compile-time choice of POOL / envWidth.  Included by
-// sgr_forward.inl, sgr_backward.inl and sgr_bwd_brdf.hip after the kernels (it needs Args, kPx and fast_ok; check_pool, pool1 and the
-// direction table's layout are in sgr_launch.h, which sgr_api.hip and sgr_loss.hip share).  No kernel and no device function lives here.
+// sgr_forward.inl, sgr_backward.inl and sgr_bwd_brdf.hip after the kernels (it needs Args, kPx and fast_ok; check_pool, pool1, the
+// direction table's layout and choose / with_flag, which need nothing of the layer, are in sgr_launch.h, which every file with an entry
+// point shares).  No kernel and no device function lives here.
 #pragma once
-#include <type_traits>
-
 #include "sgr_fast.inl"
 
 namespace sgr {
@@ -28,13 +27,9 @@ static inline bool heads_ok(const Args& a) { return fast_ok(a) && !sgr_generic_f
 static inline int half_wave_tiles(int R, int C) { return (R * C + kPx - 1) / kPx; }
 static inline dim3 half_wave_grid(int bn, int R, int C) { return dim3((unsigned)(bn * half_wave_tiles(R, C))); }
 
-// A run-time value chosen between two template arguments: f is a generic lambda whose parameter carries the constant,
+// the layer's two run-time choices of a template argument (choose, sgr_launch.h):
 //   with_pool(pool1(a), [&](auto P) { hipLaunchKernelGGL((kernel<P()>), ...); });
-// Both branches are instantiated, exactly as by the if / else this replaces.
-template <int N> using Int = std::integral_constant<int, N>;
-template <class A, class B, class F> static inline auto choose(bool first, F&& f) { return first ? f(A{}) : f(B{}); }
 template <class F> static inline auto with_pool(bool p1, F&& f) { return choose<Int<1>, Int<2>>(p1, f); }
 template <class F> static inline auto with_ew(int ew, F&& f) { return choose<Int<16>, Int<32>>(ew == 16, f); }      // after fast_ok
-template <class F> static inline auto with_flag(bool on, F&& f) { return choose<std::true_type, std::false_type>(on, f); }
 
 }  // namespace sgr

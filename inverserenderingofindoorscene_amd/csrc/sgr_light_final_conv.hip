@@ -458,12 +458,12 @@ extern "C" int sgr_light_final_conv_fwd(const float* y, const float* weight, con
   const dim3 grid(tilesX * tilesY, B), block(kLfThreads);
   const size_t lds = sizeof(float) * 2 * ((size_t)kLfKC * kLfPlane + (size_t)9 * kLfKC * lf_wpitch(NT));
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = W % 4 == 0 && aligned16({out});
-#define LF_FWD(N, V) hipLaunchKernelGGL((lf_fwd_kernel<N, V>), grid, block, lds, st, y, ys, weight, bias, out, C, O, H, W, tilesX)
-#define LF_FWD_N(N) do { if (vec) LF_FWD(N, true); else LF_FWD(N, false); } while (0)
-  if (NT == 1) LF_FWD_N(1); else if (NT == 2) LF_FWD_N(2); else LF_FWD_N(3);
-#undef LF_FWD_N
-#undef LF_FWD
+  auto fwd = [&](auto N) {
+    with_flag(W % 4 == 0 && aligned16({out}), [&](auto VEC) {
+      hipLaunchKernelGGL((lf_fwd_kernel<N(), VEC()>), grid, block, lds, st, y, ys, weight, bias, out, C, O, H, W, tilesX);
+    });
+  };
+  if (NT == 1) fwd(Int<1>{}); else if (NT == 2) fwd(Int<2>{}); else fwd(Int<3>{});
   return sgr_check((int)hipGetLastError(), "sgr_light_final_conv_fwd");
 }
 
@@ -480,10 +480,9 @@ extern "C" int sgr_light_final_conv_bwd(const float* g, const float* y, const fl
   if (dy) {
     const int tilesX = (W + kLfTW - 1) / kLfTW, tilesY = (H + kLfTHb - 1) / kLfTHb;
     const dim3 grid(tilesX * tilesY, B, (C + kLfPassC - 1) / kLfPassC), block(kLfThreads);
-    if (W % 4 == 0 && aligned16({dy}))
-      hipLaunchKernelGGL(lf_bwd_data_kernel<true>, grid, block, 0, st, g, weight, dy, C, O, H, W, tilesX);
-    else
-      hipLaunchKernelGGL(lf_bwd_data_kernel<false>, grid, block, 0, st, g, weight, dy, C, O, H, W, tilesX);
+    with_flag(W % 4 == 0 && aligned16({dy}), [&](auto VEC) {
+      hipLaunchKernelGGL(lf_bwd_data_kernel<VEC()>, grid, block, 0, st, g, weight, dy, C, O, H, W, tilesX);
+    });
   }
   SGR_SUPPORTED(!dweight || (long long)B * lf_w_strips(H, W) < (1ll << 31), "sgr_light_final_conv_bwd: B * H * W out of range for dweight");
   if (dweight) {
@@ -492,11 +491,12 @@ extern "C" int sgr_light_final_conv_bwd(const float* g, const float* y, const fl
     // 32 channels at a time where C allows: 18 (channel sub-block, tap) pairs over the four waves
     const bool wide = C % 32 == 0;
     const dim3 grid(strips, C / (wide ? 32 : 16), B);
-#define LF_BWD_W(N, CBT) hipLaunchKernelGGL((lf_bwd_w_kernel<N, CBT>), grid, dim3(kLfThreads), 0, st, g, y, ys, workspace, C, O, H, W, tilesX, tiles)
-    if (NT == 1) { if (wide) LF_BWD_W(1, 2); else LF_BWD_W(1, 1); }
-    else if (NT == 2) { if (wide) LF_BWD_W(2, 2); else LF_BWD_W(2, 1); }
-    else { if (wide) LF_BWD_W(3, 2); else LF_BWD_W(3, 1); }
-#undef LF_BWD_W
+    auto bwd_w = [&](auto N) {
+      choose<Int<2>, Int<1>>(wide, [&](auto CBT) {
+        hipLaunchKernelGGL((lf_bwd_w_kernel<N(), CBT()>), grid, dim3(kLfThreads), 0, st, g, y, ys, workspace, C, O, H, W, tilesX, tiles);
+      });
+    };
+    if (NT == 1) bwd_w(Int<1>{}); else if (NT == 2) bwd_w(Int<2>{}); else bwd_w(Int<3>{});
     const int n = 9 * C * 16 * NT;
     hipLaunchKernelGGL(lf_bwd_w_fold_kernel, dim3((n + kLfThreads - 1) / kLfThreads), dim3(kLfThreads), 0, st, workspace, dweight, B * strips, C, O, 16 * NT);
   }
