@@ -720,6 +720,36 @@ int sgr_encoder_conv_cat_fwd(int S, const float* const* xs, const int* channels,
 int sgr_encoder_conv_cat_bwd(int S, const float* g, const float* const* xs, const int* channels, const long long* strides, const float* weight,
                              float* const* dxs, float* dweight, float* dbias, float* workspace, int B, int O, int H, int W, int pad_mode, void* stream);
 
+/* ---- the synthetic loader's batch preparation (dataLoader.py:118-154, 251-259, 286-310) ----
+ * What BatchLoader.__getitem__ computes per sample between the decoded, resized files and the dataBatch tensors, for a whole batch on the
+ * device.  Inputs of the training step: no adjoints.  uint8 tensors are HWC as PIL hands them over, fp32 ones as the HDR reader does.
+ * No float atomics and nothing across workgroups: bit-identical runs, image b independent of the batch; nothing visits the host, so every
+ * call captures in a HIP graph.  A size the kernels do not serve returns SGR_ERR_UNSUPPORTED with a message that names the numpy
+ * composition of the reference, and launches nothing. */
+
+/* seg_u8 [bn,H,W,Cin], channel 0: seg = 0.5 ((u8 - 127.5) / 127.5 + 1) in fp32; segArea = 0.49 < seg < 0.51, segEnv = seg < 0.1,
+ * segObj = seg > 0.9, with erode != 0 eroded by a 7 x 7 box whose outside counts as set.  Outputs [bn,1,H,W] fp32 of exact 0 / 1. */
+int sgr_loader_masks(const unsigned char* seg_u8, float* segArea, float* segEnv, float* segObj, int bn, int H, int W, int Cin, int erode,
+                     void* stream);
+
+/* hdr [bn,H,W,3] fp32.  v[b] = element k (0-based) of the ascending sort of hdr * seg (seg as above, broadcast over the channels): a radix
+ * select over the order-preserving integer image of the floats, one workgroup per image.  scale[b] = num[b] / max(v[b], 0.1f); num NULL
+ * means fp32(0.95 - 0.05), the TEST rule.  im [bn,3,H,W] = clip(scale hdr, 0, 1) with the channel axis reversed.  NaN / inf in hdr are
+ * outside the domain (v is then some element of the data; nothing faults). */
+int sgr_loader_scale_hdr(const float* hdr, const unsigned char* seg_u8, const float* num, float* im, float* scale, float* v, int bn, int H,
+                         int W, int Cin, long long k, void* stream);
+
+/* albedo = (0.5 ((u8 - 127.5) / 127.5 + 1))^2.2 and normal = n / sqrt(max(|n|^2, 1e-5)) from [bn,H,W,3], rough = channel 0 of
+ * (u8 - 127.5) / 127.5 from [bn,H,W,rough_channels]; outputs [bn,C,H,W].  A NULL input is not wanted (at least one is). */
+int sgr_loader_brdf_maps(const unsigned char* albedo_u8, const unsigned char* normal_u8, const unsigned char* rough_u8, float* albedo,
+                         float* normal, float* rough, int bn, int H, int W, int rough_channels, void* stream);
+
+/* env_raw [bn, rawH = R 16, rawW = C 32, 3] -> out [bn,3,R,C,envHeight,envWidth], 8 x 16 (the mean of 2 x 2 blocks,
+ * ((a00 + a01) + (a10 + a11)) * 0.25f) or 16 x 32, times scale[b]; output channel k is file channel k.  env_ind [bn] (NULL: all ones):
+ * an image with env_ind[b] == 0 gives exact zeros and its raw block is not read.  env_raw and out are 16-byte aligned. */
+int sgr_loader_envmaps(const float* env_raw, const float* scale, const float* env_ind, float* out, int bn, int rawH, int rawW, int envHeight,
+                       int envWidth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,10 @@ SIGNATURES = {
     "sgr_encoder_conv_bwd": ([_P] * 7 + [_I] * 5 + [_P, _I, _P], c_int),
     "sgr_encoder_conv_cat_fwd": ([_I] + [_P] * 6 + [_I] * 5 + [_P], c_int),
     "sgr_encoder_conv_cat_bwd": ([_I] + [_P] * 9 + [_I] * 5 + [_P], c_int),
+    "sgr_loader_masks": ([_P] * 4 + [_I] * 5 + [_P], c_int),
+    "sgr_loader_scale_hdr": ([_P] * 6 + [_I] * 4 + [c_longlong, _P], c_int),
+    "sgr_loader_brdf_maps": ([_P] * 6 + [_I] * 4 + [_P], c_int),
+    "sgr_loader_envmaps": ([_P] * 4 + [_I] * 5 + [_P], c_int),
 }
 
 _lib = None

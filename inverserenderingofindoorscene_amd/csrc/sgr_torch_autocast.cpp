@@ -113,6 +113,8 @@ constexpr const char* kFp32Ops[] = {
     // sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp (the resize form), sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp
     "gn_resize", "gn_resize_bwd", "gn_resize_siblings", "gn_resize_siblings_bwd", "final_conv", "final_conv_bwd", "light_final_conv", "light_final_conv_bwd", "encoder_conv", "encoder_conv_bwd",
     "encoder_conv_cat", "encoder_conv_cat_bwd",
+    // sgr_torch_loader_prep.cpp (the uint8 inputs are no floating tensors: the casts pass them by)
+    "loader_masks", "loader_scale_hdr", "loader_brdf_maps", "loader_envmaps",
 };
 
 }  // namespace
