@@ -750,6 +750,42 @@ int sgr_loader_brdf_maps(const unsigned char* albedo_u8, const unsigned char* no
 int sgr_loader_envmaps(const float* env_raw, const float* scale, const float* env_ind, float* out, int bn, int rawH, int rawW, int envHeight,
                        int envWidth, void* stream);
 
+/* ---- testReal's output stage and the image writers (testReal.py:542-657, utils.py:65-76, 102-154) ----
+ * From fp32 predictions on the device to tensors that are ready to write: uint8 HWC images and the env image's .npz layout.  No adjoints.
+ * No float atomics and nothing across images: bit-identical runs, image b independent of its batch; nothing visits the host, so every
+ * call captures in a HIP graph.  A refusal launches nothing. */
+#define SGR_EXPORT_ALBEDO 0       /* C 3: t = 255 (x scale[b])^(1/2.2), resized                                     :544-556, 591-601 */
+#define SGR_EXPORT_NORMAL 1       /* C 3: t = 255 * 0.5 (n + 1), resized                                            :559-567 */
+#define SGR_EXPORT_ROUGH 2        /* C 1: t = 255 * 0.5 (r + 1), resized                                            :570-575, 604-609 */
+#define SGR_EXPORT_DEPTH 3        /* C 1: d = x / max(mean(x[b]), 1e-10) * 3, resized; t = 255 / clip(d + 1, 1e-6, 10)   :578-587, 612-621 */
+#define SGR_EXPORT_RENDERED 4     /* C 3: a = (x / max(x[b]))^(1/2.2), resized; t = clip(a, 0, 1) * 255              :649-657 */
+#define SGR_EXPORT_SHADING 5      /* C 3: t = 255 clip(x / mean(x[b]) / 3, 0, 1)^(1/2.2), no resize                  :638-643 */
+#define SGR_EXPORT_IMAGE 6        /* C 1 or 3 (1: three equal channels): t = 255 clip(x, 0, 1), no resize            utils.py:65-76 */
+#define SGR_EXPORT_IMAGE_GAMMA 7  /*                                     t = 255 clip(x, 0, 1)^(1/2.2), no resize */
+
+/* Floats of workspace sgr_export_image needs for `kind` (0: none -- the kind has no statistic); negative = SGR_ERR_*. */
+long long sgr_export_image_workspace_floats(int kind, int B);
+
+/* x [B,C,h,w] fp32, read through its element strides (x_strides: four long long, host memory, read during the call) -> out
+ * [B,nh,nw,Cout] uint8, contiguous; Cout = C, for the two image kinds 3.  byte = (uint8) min(max(t, 0), 255) by truncation, a NaN gives 0.
+ * The resize is OpenCV's INTER_LINEAR for float data: per axis f = (float)((d + 0.5) * ((double)in / out) - 0.5), s = floor(f), f -= s,
+ * s < 0 -> (0, 0), s >= in - 1 -> (in - 1, 0); columns first, S[s] (1 - f) + S[s + 1] f, then rows, in fp32.  Kinds without a resize
+ * need (nh, nw) == (h, w).  scale [B] (albedo only; NULL: 1).  bgr != 0 reverses the channels.  1 / 2.2 is formed in double and used as
+ * fp32.  A kind with a statistic runs one more launch that leaves 64 partials per image in `workspace`. */
+int sgr_export_image(const float* x, const long long* x_strides, const float* scale, unsigned char* out, float* workspace, int kind, int B, int C,
+                     int h, int w, int nh, int nw, int bgr, void* stream);
+
+/* utils.writeEnvToFile for every image: env [B,3,R,C,eh,ew] read through its six element strides -> out [B,Hm,Wm,3] uint8.  interY =
+ * R / nrows, interX = C / ncols; cells r = 0, interY, .. and c = 0, interX, .. give ceil(R / interY) x ceil(C / interX) tiles (that can be
+ * more than nrows x ncols), tile (i, j) at (i (eh + gap), j (ew + gap)); Hm = tiles_y (eh + gap) + gap, Wm alike; background 255;
+ * t = 255 clip(v, 0, 1)^(1/2.2).  nrows > R or ncols > C is SGR_ERR_BAD_ARG.  Cells that are not sampled are not read. */
+int sgr_export_env_mosaic(const float* env, const long long* env_strides, unsigned char* out, int B, int R, int C, int eh, int ew, int nrows,
+                          int ncols, int gap, int bgr, void* stream);
+
+/* env [B,3,R,C,eh,ew] contiguous -> out [B,R,C,eh,ew,3], out[..., j] = env[:, flip ? 2 - j : j]: exact copies.  128-bit accesses when
+ * eh ew % 4 == 0 and both pointers are 16-byte aligned, element by element otherwise. */
+int sgr_export_env_hwc(const float* env, float* out, int B, int R, int C, int eh, int ew, int flip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

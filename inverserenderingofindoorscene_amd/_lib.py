@@ -132,6 +132,10 @@ SIGNATURES = {
     "sgr_loader_scale_hdr": ([_P] * 6 + [_I] * 4 + [c_longlong, _P], c_int),
     "sgr_loader_brdf_maps": ([_P] * 6 + [_I] * 4 + [_P], c_int),
     "sgr_loader_envmaps": ([_P] * 4 + [_I] * 5 + [_P], c_int),
+    "sgr_export_image_workspace_floats": ([_I, _I], c_longlong),
+    "sgr_export_image": ([_P] * 5 + [_I] * 8 + [_P], c_int),
+    "sgr_export_env_mosaic": ([_P] * 3 + [_I] * 9 + [_P], c_int),
+    "sgr_export_env_hwc": ([_P] * 2 + [_I] * 6 + [_P], c_int),
 }
 
 _lib = None

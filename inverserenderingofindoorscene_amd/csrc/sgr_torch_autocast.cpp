@@ -115,6 +115,8 @@ constexpr const char* kFp32Ops[] = {
     "encoder_conv_cat", "encoder_conv_cat_bwd",
     // sgr_torch_loader_prep.cpp (the uint8 inputs are no floating tensors: the casts pass them by)
     "loader_masks", "loader_scale_hdr", "loader_brdf_maps", "loader_envmaps",
+    // sgr_torch_export.cpp
+    "export_image", "export_env_mosaic", "export_env_hwc",
 };
 
 }  // namespace
