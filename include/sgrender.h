@@ -786,6 +786,30 @@ int sgr_export_env_mosaic(const float* env, const long long* env_strides, unsign
  * eh ew % 4 == 0 and both pointers are 16-byte aligned, element by element otherwise. */
 int sgr_export_env_hwc(const float* env, float* out, int B, int R, int C, int eh, int ew, int flip, void* stream);
 
+/* ---- the real-image loaders' batch preparation (nyuDataLoader.py:75-131, iiwDataLoader.py:136-137, 205-214) ----
+ * From the decoded files, in the readers' layout, to the fp32 CHW tensors of the batch.  Inputs of the training step: no adjoints.  No
+ * atomics and nothing across images: bit-identical runs, image b independent of its batch; nothing visits the host, so every call captures
+ * in a HIP graph.  A refusal launches nothing. */
+
+/* im_u8, normal_u8, seg_u8 [bn,Hs,Ws,3] uint8 in cv2.imread's channel order, depth [bn,Hs,Ws] fp32 -> normal [bn,3,H,W], depth, segNormal,
+ * segDepth [bn,1,H,W], im [bn,3,H,W], contiguous fp32, in ONE launch.  Per source pixel, in fp32: output channel k of im and normal is file
+ * channel 2 - k; im0 = 0.5 ((2 (u8 / 255)^2.2 - 1) + 1); n = (u8 - 127.5) / 127.5, n / sqrt(max(|n|^2, 1e-5)); segNormal0 =
+ * 0.5 ((u8 - 127.5) / 127.5 + 1) of file channel 2.  crop [bn,4] int32 = (rs, cs, cropH, cropW): the array that is resized; NULL: the whole
+ * source.  The kernel cannot refuse a rectangle it reads from device memory: one that leaves the source is moved and cut to lie inside it
+ * (rs to [0, Hs - 1], cropH to [1, Hs - rs], columns alike), so nothing outside the source is ever read.  The resize to (H, W) is OpenCV's
+ * INTER_LINEAR for float data (sgr_export_image above), the border clamp against the crop; equal sizes give the mapped values unchanged.
+ * After it: segDepth = (depth > 1) && (depth < 10) as 0 / 1; normal / max(|normal|, 1e-5).  flip [bn] bytes (non-zero: output column x
+ * takes column W - 1 - x in all five outputs and normal[0] is negated).  colour [bn,3] double: im = (float)((double)im * colour[b][c]).
+ * crop, flip and colour come all three (TRAIN) or not at all (TEST).  128-bit stores when W % 4 == 0 and every output is 16-byte aligned. */
+int sgr_nyu_prepare(const unsigned char* im_u8, const unsigned char* normal_u8, const unsigned char* seg_u8, const float* depth, const int* crop,
+                    const unsigned char* flip, const double* colour, float* out_normal, float* out_depth, float* out_seg_normal,
+                    float* out_seg_depth, float* out_im, int bn, int Hs, int Ws, int H, int W, void* stream);
+
+/* im_u8 [bn,H,W,3] uint8 in PIL's channel order (resized and cropped on the host) -> out [bn,3,H,W] fp32 = (u8 / 255)^2.2 divided by its
+ * maximum over the image, which is the value of the image's largest byte.  An all-black image gives 0 / 0 = NaN, as numpy does.
+ * workspace: 64 * bn floats (the first launch leaves 64 partial maxima per image there). */
+int sgr_iiw_image(const unsigned char* im_u8, float* out, float* workspace, int bn, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,8 @@ SIGNATURES = {
     "sgr_export_image": ([_P] * 5 + [_I] * 8 + [_P], c_int),
     "sgr_export_env_mosaic": ([_P] * 3 + [_I] * 9 + [_P], c_int),
     "sgr_export_env_hwc": ([_P] * 2 + [_I] * 6 + [_P], c_int),
+    "sgr_nyu_prepare": ([_P] * 12 + [_I] * 5 + [_P], c_int),
+    "sgr_iiw_image": ([_P] * 3 + [_I] * 3 + [_P], c_int),
 }
 
 _lib = None

@@ -117,6 +117,8 @@ constexpr const char* kFp32Ops[] = {
     "loader_masks", "loader_scale_hdr", "loader_brdf_maps", "loader_envmaps",
     // sgr_torch_export.cpp
     "export_image", "export_env_mosaic", "export_env_hwc",
+    // sgr_torch_real_loader.cpp (uint8, int32 and bool inputs are no floating tensors and the casts leave float64 alone: colour stays double)
+    "nyu_prepare", "iiw_image",
 };
 
 }  // namespace
