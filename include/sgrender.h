@@ -810,6 +810,41 @@ int sgr_nyu_prepare(const unsigned char* im_u8, const unsigned char* normal_u8, 
  * workspace: 64 * bn floats (the first launch leaves 64 partial maxima per image there). */
 int sgr_iiw_image(const unsigned char* im_u8, float* out, float* workspace, int bn, int H, int W, void* stream);
 
+/* ---- the evaluation metrics of the reference (CompareWHDR.py:8-66, CompareNormal.py:18-42, CompareDepth.py:16-32) ----
+ * From the predictions on the device to one number per image.  Contract: DESIGN.md section 8o.  No float atomics, sums in double in a fixed
+ * order: bit-identical runs, image b independent of its batch; nothing visits the host, so every call captures in a HIP graph.  A refusal
+ * launches nothing. */
+
+/* reflectance: fp32 (is_u8 == 0) or bytes (is_u8 != 0: divided by 255 in the kernel, the saved PNG's route), three channels, addressed by
+ * strides [4] = (image, channel, row, column) in ELEMENTS -- [B,3,H,W] and [B,H,W,3] alike.  point int32 [B,N,4] = (r1, c1, r2, c2), weight
+ * fp32 [B,N], label int32 [B,N] (0 'E', 1 '1', 2 '2'), num int32 [B] (clamped to 0..N; entries at or beyond it are ignored whatever they
+ * hold).  Per judgement l = max(1e-10, (c0 + c1 + c2) / 3) in fp32; '1' if l2 / l1 > 1 + delta, else '2' if l1 / l2 > 1 + delta, else 'E'.
+ * A weight <= 0 is skipped; a label outside 0..2 or a row or column outside the image counts as weight 0 and is never dereferenced.
+ * sums [B,6] doubles = error, error_equal, error_inequal, weight, weight_equal, weight_inequal; out3 [3,B] fp32 = error / weight (0 / 0 = NaN
+ * where the reference returns None), error_equal / (weight_equal + 1e-10), error_inequal / (weight_inequal + 1e-10). */
+int sgr_eval_whdr(const void* reflectance, const long long* strides, int is_u8, const int* point, const float* weight, const int* label,
+                  const int* num, double* sums, float* out3, int B, int H, int W, int N, float delta, void* stream);
+
+/* doubles of the `partials` workspace of the two entries below: 64 * per * B with per = 3 (normal angle) or 5 (depth) */
+long long sgr_eval_partials_doubles(int B, int per);
+
+/* normal_pred fp32 [B,3,h,w] by strides [4] in elements, resized to H x W by OpenCV's INTER_LINEAR rule and NOT renormalised; normal_gt uint8
+ * [B,H,W,3] contiguous in RGB order, gt = (byte - 127.5) / 127.5 divided by its norm; mask uint8 [B,H,W,mask_channels] contiguous
+ * (mask_channels 1 or 3): a pixel counts when the minimum of its channels == 255.  theta [B,H,W] fp32 = acos(clip(dot, -1, 1)) / pi * 180 at
+ * EVERY pixel (workspace and error image), keys [B,H,W] uint32 and partials (64 * 3 * B doubles): workspaces.  mean [B] = the double sum of
+ * the counted angles / count; median [B] = numpy's (the middle element, or (a + b) * 0.5f of the two middle ones, by a radix select of both
+ * ranks in one run); count [B] int32.  count == 0, or a NaN among the counted angles: NaN for both. */
+int sgr_eval_normal_angle(const float* normal_pred, const long long* strides, const unsigned char* normal_gt, const unsigned char* mask,
+                          int mask_channels, float* theta, unsigned* keys, double* partials, float* mean, float* median, int* count, int B,
+                          int h, int w, int H, int W, void* stream);
+
+/* depth_pred fp32 [B,h,w] and depth_gt fp32 [B,H,W], each by strides [3] = (image, row, column) in elements; the prediction is resized to
+ * H x W by OpenCV's rule.  mask = 1 < gt < 10 (strict); both maps become log(x + 1e-20) in fp32 and lose their mean over ALL pixels;
+ * rmse [B] = sqrt(sum mask (d - g)^2 / sum mask), from five double sums in one pass; count [B] int32 = sum mask; an empty mask gives NaN.
+ * partials: 64 * 5 * B doubles. */
+int sgr_eval_depth_log_rmse(const float* depth_pred, const long long* pred_strides, const float* depth_gt, const long long* gt_strides,
+                            double* partials, float* rmse, int* count, int B, int h, int w, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,10 @@ SIGNATURES = {
     "sgr_export_env_hwc": ([_P] * 2 + [_I] * 6 + [_P], c_int),
     "sgr_nyu_prepare": ([_P] * 12 + [_I] * 5 + [_P], c_int),
     "sgr_iiw_image": ([_P] * 3 + [_I] * 3 + [_P], c_int),
+    "sgr_eval_whdr": ([_P, _P, _I] + [_P] * 6 + [_I] * 4 + [_F, _P], c_int),
+    "sgr_eval_partials_doubles": ([_I, _I], c_longlong),
+    "sgr_eval_normal_angle": ([_P] * 4 + [_I] + [_P] * 6 + [_I] * 5 + [_P], c_int),
+    "sgr_eval_depth_log_rmse": ([_P] * 7 + [_I] * 5 + [_P], c_int),
 }
 
 _lib = None

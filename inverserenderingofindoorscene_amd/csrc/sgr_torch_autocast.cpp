@@ -119,6 +119,8 @@ constexpr const char* kFp32Ops[] = {
     "export_image", "export_env_mosaic", "export_env_hwc",
     // sgr_torch_real_loader.cpp (uint8, int32 and bool inputs are no floating tensors and the casts leave float64 alone: colour stays double)
     "nyu_prepare", "iiw_image",
+    // sgr_torch_eval_metrics.cpp (bytes and integers pass the casts by; a bf16 prediction is widened to fp32, the kernels' only type)
+    "eval_whdr", "eval_normal_angle", "eval_depth_log_rmse",
 };
 
 }  // namespace
