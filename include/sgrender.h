@@ -845,6 +845,45 @@ int sgr_eval_normal_angle(const float* normal_pred, const long long* strides, co
 int sgr_eval_depth_log_rmse(const float* depth_pred, const long long* pred_strides, const float* depth_gt, const long long* gt_strides,
                             double* partials, float* rmse, int* count, int B, int h, int w, int H, int W, void* stream);
 
+/* ---- PIL's antialiased resize of 8-bit images (dataLoader.py:223-224, iiwDataLoader.py:112-134: Image.resize(size, Image.ANTIALIAS)) ----
+ * uint8 HWC in, uint8 HWC out: the bytes Pillow's ImagingResample gives, by integer arithmetic on a table of fixed-point coefficients
+ * (22 fractional bits) that the host builds in double.  Contract: DESIGN.md section 8p.  filter: PIL's codes, 1 lanczos (the reference's
+ * ANTIALIAS), 2 bilinear, 3 bicubic, 4 box, 5 hamming; 0 (nearest) is another code path of PIL's and is refused.  The source box is the whole
+ * image; reducing_gap is not offered.  No atomics, nothing across images: bit-identical runs, image b independent of its batch; a call does
+ * no host-device traffic, so it captures in a HIP graph.  A refusal launches nothing. */
+#define SGR_PIL_RESIZE_AUTO 0
+#define SGR_PIL_RESIZE_TWO_PASS 1     /* a launch per pass that runs, a uint8 intermediate in the workspace */
+#define SGR_PIL_RESIZE_TILED 2        /* one launch, both passes through LDS; SGR_ERR_UNSUPPORTED where the tiles do not fit */
+
+/* ints of one axis' table: 4 + 2 out_size + out_size ksize, ksize = 2 ceil(support max(in_size / out_size, 1)) + 1; negative = SGR_ERR_*. */
+long long sgr_pil_resize_table_ints(int in_size, int out_size, int filter);
+
+/* Host function, host memory: table[0] = ksize, [1] = 1 when some |k| >= 2^23 (the kernels then multiply in 32 bits, not 24), [2] = in_size,
+ * [3] = out_size, then (xmin, xmax) per output index, then ksize coefficients per output index (zero past xmax).  In double, libm's sin and
+ * cos, operation by operation as PIL.  SGR_ERR_UNSUPPORTED when a row has 2^21 + 255 sum |k| > 2^31 - 1 (the int32 sum could overflow). */
+int sgr_pil_resize_table(int in_size, int out_size, int filter, int* table);
+
+/* window: NULL (the whole resized image) or four ints (r0, c0, h, w), host memory: only that rectangle is computed.  Bytes of workspace
+ * sgr_pil_resize_u8 needs on the two_pass route: bn x (the source rows the window's rows read) x (w C rounded up to 4) when both passes
+ * run, else 0; negative = SGR_ERR_*. */
+long long sgr_pil_resize_workspace_bytes(int bn, int H, int W, int C, int outH, int outW, const int* window, int filter);
+
+/* 1 where the tiled route takes this geometry: both passes run, ksize <= 32 on both axes and the source extent of every 16 x 64 tile of the
+ * window fits its LDS tiles (24 KiB of source bytes, 12 KiB of horizontally resized bytes); 0 otherwise; negative = SGR_ERR_*. */
+int sgr_pil_resize_tiled_fits(int H, int W, int C, int outH, int outW, const int* window, int filter);
+
+/* The route SGR_PIL_RESIZE_AUTO takes: SGR_PIL_RESIZE_TILED where the geometry fits and the launch has at least 256 tiles (bn x tiles of the
+ * window; where tiled measured faster beyond the spread), else SGR_PIL_RESIZE_TWO_PASS; negative = SGR_ERR_*. */
+int sgr_pil_resize_route(int bn, int H, int W, int C, int outH, int outW, const int* window, int filter);
+
+/* src [bn,H,W,C] uint8 contiguous, C 1 or 3 -> dst [bn,h,w,C] uint8 contiguous, the window of the image resized to outH x outW (dst ==
+ * resize-then-slice).  htable / vtable: the tables of (W, outW) and (H, outH) in DEVICE memory; NULL allowed for an axis whose size does not
+ * change (that pass is skipped, not run as an identity; equal sizes copy).  The horizontal pass runs first, over the source rows the window's
+ * rows read only, and is rounded to uint8 before the vertical pass.  workspace: device memory, may be NULL when the route needs none.
+ * Bounds read from a table are cut to the source before use: a table that is not the geometry's gives wrong bytes, never a wild access. */
+int sgr_pil_resize_u8(const unsigned char* src, int bn, int H, int W, int C, unsigned char* dst, int outH, int outW, const int* window,
+                      int filter, const int* htable, const int* vtable, unsigned char* workspace, int path, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,12 @@ SIGNATURES = {
     "sgr_eval_partials_doubles": ([_I, _I], c_longlong),
     "sgr_eval_normal_angle": ([_P] * 4 + [_I] + [_P] * 6 + [_I] * 5 + [_P], c_int),
     "sgr_eval_depth_log_rmse": ([_P] * 7 + [_I] * 5 + [_P], c_int),
+    "sgr_pil_resize_table_ints": ([_I] * 3, c_longlong),
+    "sgr_pil_resize_table": ([_I] * 3 + [_P], c_int),
+    "sgr_pil_resize_workspace_bytes": ([_I] * 6 + [_P, _I], c_longlong),
+    "sgr_pil_resize_tiled_fits": ([_I] * 5 + [_P, _I], c_int),
+    "sgr_pil_resize_route": ([_I] * 6 + [_P, _I], c_int),
+    "sgr_pil_resize_u8": ([_P] + [_I] * 4 + [_P, _I, _I, _P, _I] + [_P] * 3 + [_I, _P], c_int),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Builds ``../libsgrender_torch.so`` -- the C++ torch extension (``sgr_torch.cpp``, ``sgr_torch_bilateral.cpp``, ``sgr_torch_brdf.cpp``,
-``sgr_torch_brdf_input.cpp``, ``sgr_torch_brdf_heads.cpp``, ``sgr_torch_gn_stage.cpp``, ``sgr_torch_gn_resize.cpp``, ``sgr_torch_gn_siblings.cpp``, ``sgr_torch_final_conv.cpp``, ``sgr_torch_light_final_conv.cpp``, ``sgr_torch_encoder_conv.cpp``, ``sgr_torch_loader_prep.cpp``, ``sgr_torch_export.cpp``, ``sgr_torch_real_loader.cpp``, ``sgr_torch_eval_metrics.cpp``, ``sgr_torch_comm.cpp``, ``sgr_torch_autocast.cpp`` and their shared header ``sgr_torch_common.hpp``: TORCH_LIBRARY(sgrender) schemas, HIP-device / Meta / Autograd kernels around the C ABI
+``sgr_torch_brdf_input.cpp``, ``sgr_torch_brdf_heads.cpp``, ``sgr_torch_gn_stage.cpp``, ``sgr_torch_gn_resize.cpp``, ``sgr_torch_gn_siblings.cpp``, ``sgr_torch_final_conv.cpp``, ``sgr_torch_light_final_conv.cpp``, ``sgr_torch_encoder_conv.cpp``, ``sgr_torch_loader_prep.cpp``, ``sgr_torch_export.cpp``, ``sgr_torch_real_loader.cpp``, ``sgr_torch_eval_metrics.cpp``, ``sgr_torch_pil_resize.cpp``, ``sgr_torch_comm.cpp``, ``sgr_torch_autocast.cpp`` and their shared header ``sgr_torch_common.hpp``: TORCH_LIBRARY(sgrender) schemas, HIP-device / Meta / Autograd kernels around the C ABI
 of libsgrender.so) -- in-tree, with one g++ invocation against the installed PyTorch-ROCm.
 
     python inverserenderingofindoorscene_amd/csrc/build_torch_ext.py [--force]
@@ -18,7 +18,7 @@ OUT = os.path.join(os.path.dirname(HERE), "libsgrender_torch.so")
 SOURCES = [os.path.join(HERE, "sgr_torch.cpp"), os.path.join(HERE, "sgr_torch_bilateral.cpp"), os.path.join(HERE, "sgr_torch_brdf.cpp"),
            os.path.join(HERE, "sgr_torch_brdf_input.cpp"), os.path.join(HERE, "sgr_torch_brdf_heads.cpp"), os.path.join(HERE, "sgr_torch_gn_stage.cpp"),
            os.path.join(HERE, "sgr_torch_gn_resize.cpp"), os.path.join(HERE, "sgr_torch_gn_siblings.cpp"), os.path.join(HERE, "sgr_torch_final_conv.cpp"), os.path.join(HERE, "sgr_torch_light_final_conv.cpp"),
-           os.path.join(HERE, "sgr_torch_encoder_conv.cpp"), os.path.join(HERE, "sgr_torch_loader_prep.cpp"), os.path.join(HERE, "sgr_torch_export.cpp"), os.path.join(HERE, "sgr_torch_real_loader.cpp"), os.path.join(HERE, "sgr_torch_eval_metrics.cpp"), os.path.join(HERE, "sgr_torch_comm.cpp"), os.path.join(HERE, "sgr_torch_autocast.cpp")]
+           os.path.join(HERE, "sgr_torch_encoder_conv.cpp"), os.path.join(HERE, "sgr_torch_loader_prep.cpp"), os.path.join(HERE, "sgr_torch_export.cpp"), os.path.join(HERE, "sgr_torch_real_loader.cpp"), os.path.join(HERE, "sgr_torch_eval_metrics.cpp"), os.path.join(HERE, "sgr_torch_pil_resize.cpp"), os.path.join(HERE, "sgr_torch_comm.cpp"), os.path.join(HERE, "sgr_torch_autocast.cpp")]
 DEPS = SOURCES + [os.path.join(HERE, "sgr_torch_common.hpp"), os.path.join(HERE, "..", "..", "include", "sgrender.h"), os.path.abspath(__file__)]
 
 

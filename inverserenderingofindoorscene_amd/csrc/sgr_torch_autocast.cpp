@@ -121,6 +121,8 @@ constexpr const char* kFp32Ops[] = {
     "nyu_prepare", "iiw_image",
     // sgr_torch_eval_metrics.cpp (bytes and integers pass the casts by; a bf16 prediction is widened to fp32, the kernels' only type)
     "eval_whdr", "eval_normal_angle", "eval_depth_log_rmse",
+    // sgr_torch_pil_resize.cpp (bytes in, bytes out: the casts pass the only tensor by, so the rule is a fall-through in effect)
+    "pil_resize",
 };
 
 }  // namespace

@@ -1,4 +1,4 @@
-// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp, sgr_torch_loader_prep.cpp, sgr_torch_export.cpp, sgr_torch_real_loader.cpp, sgr_torch_eval_metrics.cpp, sgr_torch_comm.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
+// What sgr_torch.cpp, sgr_torch_bilateral.cpp, sgr_torch_brdf.cpp, sgr_torch_brdf_input.cpp, sgr_torch_brdf_heads.cpp, sgr_torch_gn_stage.cpp, sgr_torch_gn_resize.cpp, sgr_torch_gn_siblings.cpp, sgr_torch_final_conv.cpp, sgr_torch_light_final_conv.cpp, sgr_torch_encoder_conv.cpp, sgr_torch_loader_prep.cpp, sgr_torch_export.cpp, sgr_torch_real_loader.cpp, sgr_torch_eval_metrics.cpp, sgr_torch_pil_resize.cpp, sgr_torch_comm.cpp and sgr_torch_autocast.cpp (one libsgrender_torch.so) share: the C ABI of libsgrender.so,
 // resolved ONCE for the whole extension, and the few helpers every operator file needs around it.
 //
 // The C ABI stays the drop-in boundary: resolved with dlopen at first use ($SGR_LIB, else the libsgrender.so next to the extension's
@@ -64,7 +64,8 @@ using T8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Te
   X(sgr_loader_masks) X(sgr_loader_scale_hdr) X(sgr_loader_brdf_maps) X(sgr_loader_envmaps)                                  \
   X(sgr_export_image_workspace_floats) X(sgr_export_image) X(sgr_export_env_mosaic) X(sgr_export_env_hwc)         \
   X(sgr_nyu_prepare) X(sgr_iiw_image)                                                                                          \
-  X(sgr_eval_whdr) X(sgr_eval_partials_doubles) X(sgr_eval_normal_angle) X(sgr_eval_depth_log_rmse)
+  X(sgr_eval_whdr) X(sgr_eval_partials_doubles) X(sgr_eval_normal_angle) X(sgr_eval_depth_log_rmse)                              \
+  X(sgr_pil_resize_table_ints) X(sgr_pil_resize_table) X(sgr_pil_resize_workspace_bytes) X(sgr_pil_resize_tiled_fits) X(sgr_pil_resize_route) X(sgr_pil_resize_u8)
 
 struct Api {
 #define SGR_DECL(name) decltype(&::name) name = nullptr;

@@ -6,7 +6,7 @@
   ``loader_envmaps(env_raw, scale, env_ind)``   :153-154, 286-310
   ``prepare_batch(raw, phase, isLight, u)``     the ``dataBatch`` dict of ``BatchLoader.__getitem__`` for a whole batch
 
-They take what the loader has DECODED AND RESIZED -- the file readers, ``cv2.resize(INTER_AREA)`` and PIL's resize stay on the host -- in the
+They take what the loader has DECODED AND RESIZED -- the file readers and ``cv2.resize(INTER_AREA)`` stay on the host; PIL's resize is ``loader_resize`` of pil_resize.py -- in the
 layout the readers hand it over (HWC), and do the per-sample arithmetic that the reference runs in numpy inside its loader workers: a masked
 order statistic, a 7 x 7 erosion, three point-wise maps and a transposing 2 x 2 block mean.  The results are inputs of the training step, so
 there is no autograd.  Nothing visits the host (``u`` given as a device tensor), two runs are bit-identical, an image does not depend on its

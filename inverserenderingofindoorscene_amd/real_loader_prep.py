@@ -4,8 +4,8 @@
   ``nyu_augmentation(u, imHeight, imWidth, ...)``                            :76-82, 121-129 (plain torch, float64)
   ``iiw_image(im_u8)``                                                       iiwDataLoader.py:136-137, 205-214
 
-They take what the loaders have DECODED -- ``cv2.imread``'s uint8 HWC arrays and the fp32 depth for NYU; for IIW the bytes PIL has resized and
-the loader has cropped -- and do the per-sample arithmetic the reference runs in numpy inside its loader workers: for NYU a random crop, the
+They take what the loaders have DECODED -- ``cv2.imread``'s uint8 HWC arrays and the fp32 depth for NYU; for IIW the resized and cropped bytes
+(``iiw_resize_crop`` of pil_resize.py, or PIL and a slice on the host) -- and do the per-sample arithmetic the reference runs in numpy inside its loader workers: for NYU a random crop, the
 byte maps, two normalisations of the normal, four ``cv2.resize(INTER_LINEAR)`` calls, two thresholds, a mirror and a colour scale, in ONE
 launch for the whole batch with one crop rectangle per image.  The results are inputs of the training step, so there is no autograd.  Nothing
 visits the host when the augmentation arguments are device tensors, two runs are bit-identical, an image does not depend on its batch, and the
@@ -143,7 +143,7 @@ def nyu_prepare_batch(raw, phase: str = "TRAIN", crop=None, flip=None, colour=No
 
 
 def iiw_image(im_u8):
-    """fp32 ``[bn,3,H,W]`` from ``im_u8 [bn,H,W,3]`` uint8 in PIL's channel order, already resized and cropped on the host (the crop is a
+    """fp32 ``[bn,3,H,W]`` from ``im_u8 [bn,H,W,3]`` uint8 in PIL's channel order, already resized and cropped (``iiw_resize_crop``, or PIL and a slice on the host; the crop is a
     slice and commutes with the point-wise maps): ``(u8 / 255) ** 2.2``, transposed to CHW and divided by its maximum over the image -- the
     ``im`` of ``iiwDataLoader.loadImage`` with ``isGama``.  The map is monotone, so the maximum is the value of the image's largest byte and a
     non-black image's maximum element is exactly 1.  AN ALL-BLACK IMAGE GIVES 0 / 0 = NaN THROUGHOUT, as numpy does in the reference."""
